@@ -7,7 +7,9 @@ per GPU, fp32, bn=local (batch statistics per rank), synthetic data: U(-1,1) ima
 image index, 1-3 injected person boxes per image for placement (the first pass still runs in full),
 synthetic weights (seed 0).
 
-  python bench.py                       # N=1
+  python bench.py                       # N=1: set up, warm up, time --steps steps, print the line
+  python bench.py --full                # + roofline of a profiled step, secondary line, CPU baseline
+  python bench.py --dump-outputs DIR    # + the last timed step's grad / params / metrics as DIR/*.npy
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 from __future__ import annotations
@@ -176,6 +178,15 @@ def main():
                          "D4 bf16, standard otherwise")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary line (the reference's own placement flow, measured after the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what takes runs of its own: the profiled step's roofline, "
+                         "the all-reduce alone (N>1), the secondary line and the CPU baseline (each still has its "
+                         "--no-* switch); without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed train_step left its caller as DIR/<name>.npy "
+                         "(float32; metrics float64): grad = [d patch | d scale] after the all-reduce, params = "
+                         "[patch | scale] after Adam + clip, metrics = the step's rank-summed metric row "
+                         "(phx.h PHX_M_*); rank r > 0 writes <name>.rank<r>.npy")
     args = ap.parse_args()
 
     # the line certifies itself: every PHX_* knob of the run goes into it, and the diagnostics that
@@ -247,13 +258,21 @@ def main():
     elapsed = float(dt.item())
     images_per_s = world * B * args.steps / elapsed
 
+    if args.dump_outputs:
+        # what the last timed train_step left its caller (nothing has run since): ~10 MB per rank
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if rank == 0 else f".rank{rank}"
+        for name, t, dt_ in (("grad", att.grad, np.float32), ("params", att.params, np.float32),
+                             ("metrics", att.metrics_buf, np.float64)):
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), t.detach().cpu().numpy().astype(dt_))
+
     patches_headline = att.step_metrics()["patches"] if rank == 0 else 0
 
     # the step's one collective timed alone (N>1): the same [d patch | d scale | metric row] payload,
     # on a copy, between barriers, max over ranks — so a scaling curve separates the exchange from
     # the per-rank compute
     allreduce = None
-    if world > 1:
+    if args.full and world > 1:
         buf = att._red.clone()
         n_ar = 20
         ddp.allreduce_sum_(buf)  # warm the communicator
@@ -277,7 +296,7 @@ def main():
 
     roofline = None
     step_roof = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         # one extra, untimed step with per-launch-group HIP events on the launch stream
         victim.ctx.profile(True)
         main_step()
@@ -303,7 +322,7 @@ def main():
     # on the first pass's soft-NMS person boxes (attacker.py:180-184) with a person prior that gives
     # ~1500 patches per step — timed the same way on a fresh victim after the headline
     secondary = None
-    if not args.no_secondary and args.placement == "injected" and args.model == "efficientdet-d0":
+    if args.full and not args.no_secondary and args.placement == "injected" and args.model == "efficientdet-d0":
         del att
         torch.cuda.empty_cache()
         v2 = EfficientDetVictim(args.model, "synthetic", seed=0, image_size=S, max_batch=B, rng_seed=0,
@@ -345,7 +364,7 @@ def main():
         att = a2
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "efficientdet-d0":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "efficientdet-d0":
         threads = min(16, len(os.sched_getaffinity(0)))
         cpu = cpu_baseline(S, args.cpu_batch, threads)
 
