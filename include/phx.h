@@ -157,6 +157,29 @@ int phx_soft_nms(phx_ctx* ctx, const float* boxes, const float* scores, const in
 int phx_brightness_match(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W,
                          int B, float* out, void* stream);
 
+/* The patch-to-scene matcher of the attack's Patcher (attacker.py:362: one word swaps
+ * BrightnessMatcher for HistogramMatcher).  MEAN (the default) transfers the Y-channel mean
+ * (brightness_matcher.py:14-73); HISTOGRAM does a full histogram specification of the printed
+ * patch's Y channel onto the scene's (brightness_matcher.py:76-162), whose gradient treats the
+ * lookup table as a constant, as TF autodiff does (the histogram op has no gradient).  The choice
+ * is read by phx_patch_images, phx_step_grad and phx_eval_step.  The defender's Masker
+ * (phx_def_*) and the inference compositor (phx_adv_patch) keep the mean matcher.  Any other
+ * value is PHX_EINVAL with a message; no device call is made.  The setting belongs to the context
+ * and is read when a call is issued: like every other call on one context it is not thread-safe, so
+ * callers that share a context (two attackers on one victim) set it before each call they issue and
+ * do not interleave calls from several threads.  Any batch size up to max_batch runs with either. */
+enum { PHX_MATCH_MEAN = 0, PHX_MATCH_HISTOGRAM = 1 };
+int phx_set_matcher(phx_ctx* ctx, int matcher);
+/* HistogramMatcher.call((src, tgt)) (brightness_matcher.py:82-115), same contract as
+ * phx_brightness_match: one src per image, no print variation.  P >= 2, H*W >= 2. */
+int phx_histogram_match(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W,
+                        int B, float* out, void* stream);
+/* Its intermediates, for exact tests: hist [B,2,256] int32 (the 256-bin Y histograms of source
+ * and target, tf.histogram_fixed_width(Y, [0,1], 256); NULL = skip) and lut [B,256], the table
+ * interpolate(cdf_tgt, floating_space, cdf_src) the pixels are remapped through (device). */
+int phx_histogram_lut(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W, int B,
+                      int32_t* hist, float* lut, void* stream);
+
 /* Patcher.call([boxes, images]) (attacker.py:490-498): print variation, brightness match,
  * placement, antialiased resize, noise, brightness jitter, ±20° rotate, composite, paste.
  * boxes [B,maxb,4] with count [B]; params = [patch | scale]; `step` keys the RNG.

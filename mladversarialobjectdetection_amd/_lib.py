@@ -24,6 +24,7 @@ NMETRIC = 9
 
 BN_LOCAL, BN_FROZEN, BN_SYNC = 0, 1, 2
 DTYPE_F32, DTYPE_BF16 = 0, 1
+MATCH_MEAN, MATCH_HISTOGRAM = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PHX_LIB selects another in-tree build (libphx*.so next to this file) for A/B timing runs
@@ -69,6 +70,11 @@ _SIGS = [
      [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_brightness_match", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("phx_set_matcher", c_int, [c_void_p, c_int]),
+    ("phx_histogram_match", c_int,
+     [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("phx_histogram_lut", c_int,
+     [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("phx_patch_images", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p,
       c_void_p, c_void_p]),

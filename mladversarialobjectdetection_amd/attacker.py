@@ -5,6 +5,7 @@ Same names, argument meaning and error behaviour as the reference where they exi
 
   EfficientDetVictim       util.get_victim_model (util.py:177-189) + KerasDriver (infer_lib.py:383)
   BrightnessMatcher.call   brightness_matcher.py:43-73
+  HistogramMatcher.call    brightness_matcher.py:82-115
   Patcher.call             attacker.py:490-498
   PatchAttacker            attacker.py:24-341: first_pass :91, second-pass loss and gradient in
                            call :172-219, calc_asr :238, train_step :307, save_weights :328
@@ -190,6 +191,8 @@ class EfficientDetVictim:
 class BrightnessMatcher:
     """brightness_matcher.BrightnessMatcher: Y-channel mean transfer patch -> scene."""
 
+    _entry = "phx_brightness_match"
+
     def __init__(self, victim: EfficientDetVictim):
         self.victim = victim
 
@@ -202,11 +205,36 @@ class BrightnessMatcher:
         tgt = tgt.contiguous().float()
         B, Pp = src.shape[0], src.shape[1]
         out = torch.empty_like(src)
-        self.victim.ctx.call("phx_brightness_match", src.data_ptr(), Pp, tgt.data_ptr(), tgt.shape[1],
+        self.victim.ctx.call(self._entry, src.data_ptr(), Pp, tgt.data_ptr(), tgt.shape[1],
                              tgt.shape[2], B, out.data_ptr(), _stream())
         return out[0] if squeeze else out
 
     call = __call__
+
+
+class HistogramMatcher(BrightnessMatcher):
+    """brightness_matcher.HistogramMatcher: histogram specification of the patch's Y channel onto the
+    scene's (256-bin CDFs, a lookup table, a per-pixel piecewise-linear remap)."""
+
+    _entry = "phx_histogram_match"
+
+    def lut(self, inputs):
+        """The intermediates of the match: (hist [B,2,256] int32 — source and target Y histograms —,
+        lut [B,256] float32)."""
+        src, tgt = inputs
+        if src.dim() == 3:
+            src, tgt = src[None], tgt[None]
+        src = src.contiguous().float()
+        tgt = tgt.contiguous().float()
+        B = src.shape[0]
+        hist = torch.empty(B, 2, 256, dtype=torch.int32, device=src.device)
+        lut = torch.empty(B, 256, device=src.device)
+        self.victim.ctx.call("phx_histogram_lut", src.data_ptr(), src.shape[1], tgt.data_ptr(), tgt.shape[1],
+                             tgt.shape[2], B, hist.data_ptr(), lut.data_ptr(), _stream())
+        return hist, lut
+
+
+MATCHERS = {"brightness": (_lib.MATCH_MEAN, BrightnessMatcher), "histogram": (_lib.MATCH_HISTOGRAM, HistogramMatcher)}
 
 
 def _withdraw_if_refilled(obj, withdraw):
@@ -252,6 +280,7 @@ class Patcher:
         B = images.shape[0]
         bx, cnt = _pad_boxes(boxes, B, images.device)
         out = torch.empty_like(images)
+        a._select_matcher()
         self.last_placements = torch.zeros(B, bx.shape[1], 8, device=images.device)
         a.model.ctx.call("phx_patch_images", images.data_ptr(), B, bx.data_ptr(), cnt.data_ptr(), bx.shape[1],
                          a.params.data_ptr(), int(a.cur_step if step is None else step), a.global_offset(B),
@@ -306,7 +335,10 @@ class PatchAttacker:
                "asr_to_scale")
 
     def __init__(self, model: EfficientDetVictim, initial_patch=None, config_override=None,
-                 visualize_freq=200, *, seed=0, learning_rate=1e-2, device=None):
+                 visualize_freq=200, *, seed=0, learning_rate=1e-2, device=None, matcher="brightness"):
+        if matcher not in MATCHERS:
+            raise ValueError("matcher must be 'brightness' (the reference's Patcher) or 'histogram'")
+        self.matcher = matcher
         self.model = model
         self.config = model.config
         if config_override:
@@ -333,7 +365,7 @@ class PatchAttacker:
         self.cur_step = 0
         self.visualize_freq = visualize_freq
         self._patcher = Patcher(self)
-        self._matcher = BrightnessMatcher(model)
+        self._matcher = MATCHERS[matcher][1](model)
         self.metrics = {k: _Mean() for k in self.METRICS}
         self._pending = []      # (step id, device metric row) not yet folded into self.metrics
         self._snapshots = {}    # step id -> running-mean dict after that step
@@ -356,6 +388,11 @@ class PatchAttacker:
     def global_offset(self, B):
         return ddp.global_offset(B)
 
+    def _select_matcher(self):
+        """The matcher is a setting of the victim's library context, which attackers may share:
+        every call that pastes patches selects this attacker's first (a host-side assignment)."""
+        self.model.ctx.call("phx_set_matcher", MATCHERS[self.matcher][0])
+
     # ---- reference methods -------------------------------------------------------------------
     def first_pass(self, images):
         return self.model.first_pass(images)
@@ -376,6 +413,7 @@ class PatchAttacker:
             self._keep = (bx, cnt)
         else:
             bp, cp, maxb = None, None, 0
+        self._select_matcher()
         if not training:
             ob = torch.empty(B, _lib.MAX_OUT, 4, device=images.device)
             os_ = torch.empty(B, _lib.MAX_OUT, device=images.device)

@@ -142,6 +142,8 @@ struct Exec {
   SpanEntry* spans = nullptr;
   double* ysum = nullptr;
   float* ymean = nullptr;
+  int* hpart = nullptr;  // histogram matcher: per-workgroup counts and the lookup tables [B,256]
+  float* hlut = nullptr;
   float *rstore = nullptr, *dstore = nullptr;
   float *matched = nullptr, *dmatched = nullptr;
   double* dsum = nullptr;
@@ -259,6 +261,7 @@ struct phx_ctx {
   float score_thresh = 0.f;
   float filter_thresh = 0.f, nms_thresh = 0.001f;
   uint64_t seed = 0;
+  int matcher = PHX_MATCH_MEAN;  // phx_set_matcher: the attack's patch-to-scene matcher
   std::vector<WeightEntry> weights;
   size_t wfloats = 0;
   std::string manifest_json;
@@ -283,7 +286,8 @@ struct phx_ctx {
   size_t aug_cap = 0;
   DPtr ap_ws;          // inference compositor scratch (phx_adv_patch)
   size_t ap_cap = 0;
-  // scratch for phx_brightness_match (Y-mean partials), grown on demand
+  // scratch for phx_brightness_match (Y-mean partials) and phx_histogram_match / phx_histogram_lut
+  // (chunk counts, lookup tables), grown on demand
   DPtr bm_ws;
   size_t bm_cap = 0;
   // executor use clock (least-recently-used eviction, see exec_for)
@@ -890,6 +894,10 @@ Exec& phx_ctx::exec_for(int B, int tag) {
   const size_t np = (size_t)PHX_PATCH_SIZE * PHX_PATCH_SIZE * 3;
   E.matched = E.alloc<float>(eot ? np * B : 1);
   E.dmatched = E.alloc<float>(eot ? np * B : 1);
+  // the histogram matcher's chunk counts (128 KB per image) and tables, held whichever matcher is
+  // selected so that no step allocates
+  E.hpart = E.alloc<int>(eot ? eot_hist_part_ints(B) : 1);
+  E.hlut = E.alloc<float>(eot ? (size_t)B * 256 : 1);
   E.dsum = E.alloc<double>((size_t)B * 64);
   E.tvs = E.alloc<double>(256);
   E.err = E.alloc<int>(1);
@@ -2269,6 +2277,71 @@ int phx_brightness_match(phx_ctx* ctx, const float* src, int P, const float* tgt
   PHX_CATCH(ctx)
 }
 
+int phx_set_matcher(phx_ctx* ctx, int matcher) {
+  if (!ctx) return PHX_EINVAL;
+  if (matcher != PHX_MATCH_MEAN && matcher != PHX_MATCH_HISTOGRAM)
+    return fail(ctx, PHX_EINVAL, "matcher must be PHX_MATCH_MEAN (0) or PHX_MATCH_HISTOGRAM (1)");
+  ctx->matcher = matcher;
+  return PHX_OK;
+}
+
+namespace {
+// scratch of the stand-alone histogram matcher (chunk counts + lookup tables), shared with
+// phx_brightness_match's
+void hist_scratch(phx_ctx* ctx, int B, hipStream_t s, int** hpart, float** lut) {
+  const size_t need = eot_hist_part_ints(B) * sizeof(int) + (size_t)B * 256 * sizeof(float);
+  if (need > ctx->bm_cap) {
+    PHX_HIP(hipStreamSynchronize(s));
+    ctx->bm_ws.reset(dalloc<char>(need));
+    ctx->bm_cap = need;
+  }
+  *hpart = reinterpret_cast<int*>(ctx->bm_ws.get());
+  *lut = reinterpret_cast<float*>(*hpart + eot_hist_part_ints(B));
+}
+EotDims match_dims(int B, int P, int H, int W) {
+  EotDims d{};
+  d.B = B;
+  d.P = P;
+  d.H = H;
+  d.W = W;
+  d.maxb = PHX_MAX_OUT;
+  d.span_stride = std::max(H, W);
+  return d;
+}
+}  // namespace
+
+int phx_histogram_match(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W,
+                        int B, float* out, void* stream) {
+  if (!ctx || !src || !tgt || !out || B <= 0 || B > ctx->max_batch || P < 2 || H <= 0 || W <= 0 ||
+      (long)H * W < 2)
+    return PHX_EINVAL;
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  int* hpart;
+  float* lut;
+  hist_scratch(ctx, B, s, &hpart, &lut);
+  launch_eot_hist_match(match_dims(B, P, H, W), src, nullptr, tgt, out, hpart, lut, false, s);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_histogram_lut(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W, int B,
+                      int32_t* hist, float* lut, void* stream) {
+  if (!ctx || !src || !tgt || !lut || B <= 0 || B > ctx->max_batch || P < 2 || H <= 0 || W <= 0 ||
+      (long)H * W < 2)
+    return PHX_EINVAL;
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  int* hpart;
+  float* own;
+  hist_scratch(ctx, B, s, &hpart, &own);
+  launch_eot_hist_lut(match_dims(B, P, H, W), src, nullptr, tgt, hpart, hist, lut, false, s);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
 int phx_letterbox(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
                   const float* mean_rgb, const float* stddev_rgb, int out_h, int out_w, float* out,
                   void* stream) {
@@ -2372,7 +2445,10 @@ void eot_forward(phx_ctx* ctx, Exec& E, const float* images, int B, const float*
   Scope scope(ctx, "eot_fwd", 0.0, (double)B * (2.0 * PHX_NPATCH + 3.0 * d.H * d.W * 3) * 4.0, s);
   launch_eot_place(d, boxes, count, params, ctx->seed, step, gimg0, E.img, E.place, E.spans, E.err,
                    s);
-  launch_eot_match(d, params, E.img, images, E.matched, E.ysum, E.ymean, true, s);
+  if (ctx->matcher == PHX_MATCH_HISTOGRAM)
+    launch_eot_hist_match(d, params, E.img, images, E.matched, E.hpart, E.hlut, true, s);
+  else
+    launch_eot_match(d, params, E.img, images, E.matched, E.ysum, E.ymean, true, s);
   launch_eot_resize(d, E.matched, E.place, E.spans, ctx->seed, step, gimg0, E.rstore, s);
   launch_eot_composite(d, images, E.place, E.rstore, E.patched, E.owner, s);
 }
@@ -2660,7 +2736,10 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
   Scope scope(ctx, "eot_bwd", 0.0, (double)B * (3.0 * PHX_NPATCH + 2.0 * d.H * d.W * 3) * 4.0, s);
   launch_eot_rot_bwd(d, dimg, E.owner, E.place, E.rstore, E.dstore, s);
   launch_eot_resize_bwd(d, E.place, E.spans, E.dstore, E.rstore, E.dmatched, s);
-  launch_eot_patch_bwd(d, params, E.img, E.ymean, E.dmatched, E.dsum, grad, add_tv != 0, s);
+  if (ctx->matcher == PHX_MATCH_HISTOGRAM)
+    launch_eot_hist_patch_bwd(d, params, E.img, E.hlut, E.dmatched, grad, add_tv != 0, s);
+  else
+    launch_eot_patch_bwd(d, params, E.img, E.ymean, E.dmatched, E.dsum, grad, add_tv != 0, s);
   launch_tv(params, PHX_PATCH_SIZE, E.tvs, metrics, add_tv != 0, s);
   ck_note(E, "grad", grad, (size_t)(PHX_NPATCH + 1) * 4, s);
   if (fork || side_nms) PHX_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));

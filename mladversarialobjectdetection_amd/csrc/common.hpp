@@ -80,6 +80,11 @@ __device__ __forceinline__ float round_bf16(float f) {
 // fix-up steps, which only act when |n| < 2^-103 or |n / d| nears the exponent limits: those (and
 // 0, inf, nan) keep the plain division, so every result equals n / d bit for bit.
 // PHX_DROP_HWDIV=1 (build flag) restores the plain division everywhere (A/B diagnostics).
+// A second user, the histogram matcher (kernels_eot.hip), calls it through div_exact below with
+// denominators in [2^-20, 2^20]: the knot spacing of its grid (about 1/255), CDF steps (down to
+// 1 / (pixels - 1)) and pixel counts.  The sequence is scale-free there as well (hipcc's own lowering
+// is this sequence between v_div_scale and v_div_fixup, which are the identity at such exponents);
+// tools/div_check compares both ranges with n / d.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float div_surv(float n, float d) {
 #if defined(PHX_DROP_HWDIV) && PHX_DROP_HWDIV
@@ -93,6 +98,14 @@ __device__ __forceinline__ float div_surv(float n, float d) {
   q = fmaf(fmaf(-d, q, n), r, q);
   return fmaf(fmaf(-d, q, n), r, q);
 #endif
+}
+// n / d, bit for bit, for any operands: div_surv where its sequence is scale-free (|d| in
+// [2^-20, 2^20] and |n| in [2^-60, 2^60], so that no residual term of the sequence goes subnormal),
+// else the plain division
+__device__ __forceinline__ float div_exact(float n, float d) {
+  const float a = fabsf(d), m = fabsf(n);
+  if (m == 0.f && a > 0.f && a <= 0x1p127f) return d < 0.f ? -n : n;  // a signed zero, no division
+  return (a >= 0x1p-20f && a <= 0x1p20f && m >= 0x1p-60f && m <= 0x1p60f) ? div_surv(n, d) : n / d;
 }
 
 // ------------------------------------------------------------------------------------------

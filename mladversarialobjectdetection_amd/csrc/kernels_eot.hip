@@ -1,6 +1,6 @@
 // kernels_eot.hip — the expectation-over-transformation patch pipeline (Patcher,
-// attacker.py:344-498; BrightnessMatcher, brightness_matcher.py:14-73) forward and backward,
-// TV loss and the Adam update.
+// attacker.py:344-498; BrightnessMatcher and HistogramMatcher, brightness_matcher.py:14-162) forward
+// and backward, TV loss and the Adam update.
 //
 // Layout / parallelisation (MI355X-first, not the reference's map_fn x while_loop):
 //   * placement of every (image, box) slot in one tiny kernel; a compact list of valid boxes and
@@ -430,6 +430,192 @@ void launch_eot_match_batch(const EotDims& d, const float* src, const ImgParams*
   PHX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_eot_match, dim3(cdiv((long)d.P * d.P, 256), d.B), dim3(256), 0, s, d, src, stride, img,
                      ymean, 1, matched);
+  PHX_LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------------------------------
+// histogram matcher (brightness_matcher.py:76-162): histogram specification of the printed patch's
+// Y channel onto the scene's.  Three launches: 256-bin histograms of both Y channels (per-workgroup
+// partial counts, no global atomics), one workgroup per image that folds them into the two CDFs and
+// the 256-entry lookup table lut = interp(cdf_t, FS, cdf_s), and the per-pixel remap
+// interp(FS, lut, Y) fused with the colour conversions.  This file compiles with FMA contraction
+// off, so every operation below rounds on its own, in the reference's order.
+// ------------------------------------------------------------------------------------------
+constexpr int kHistBins = 256;
+static constexpr int kHistChunks = 64;  // workgroups per (image, side), as k_eot_ysum's kYChunks
+
+// FS[k]: tf.clip_by_value(tf.range(0., 1.00001, 1/255), 0, 1) taken as k * f32(1/255)
+__device__ __forceinline__ float hist_fs(int k) {
+  return fminf(fmaxf((float)k * (1.0f / 255.0f), 0.0f), 1.0f);
+}
+
+// tf.histogram_fixed_width(v, [0, 1], 256): clamp(floor(256 v), 0, 255)
+__device__ __forceinline__ int hist_bin(float v) {
+  return (int)fminf(fmaxf(floorf(256.0f * v), 0.0f), 255.0f);
+}
+
+// z = 0 source (printed patch), z = 1 target (image): each workgroup counts its grid-stride share of
+// the pixels into one LDS histogram per wave (pixels of natural images pile into a few bins; the
+// copies keep the waves off each other's counters) and stores the folded 256 counts
+__global__ __launch_bounds__(256) void k_eot_hist(EotDims d, const float* __restrict__ src,
+                                                  long src_stride, const ImgParams* __restrict__ img,
+                                                  const float* __restrict__ tgt, int apply,
+                                                  int* __restrict__ hpart) {
+  __shared__ unsigned int sh[4][kHistBins];
+  const int b = blockIdx.y, z = blockIdx.z, t = threadIdx.x;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) sh[w][t] = 0u;
+  __syncthreads();
+  const long npx = z == 0 ? (long)d.P * d.P : (long)d.H * d.W;
+  const ImgParams p = img ? img[b] : ImgParams{};
+  const float* base = z == 0 ? src + (long)b * src_stride : tgt + (long)b * d.H * d.W * 3;
+  unsigned int* mine = sh[t >> 6];
+  for (long i = (long)blockIdx.x * blockDim.x + t; i < npx; i += (long)gridDim.x * blockDim.x) {
+    float r, g, bl;
+    if (z == 0) {
+      r = (print_px(base, p, i * 3 + 0, 0, apply) + 1.0f) * kTo01;
+      g = (print_px(base, p, i * 3 + 1, 1, apply) + 1.0f) * kTo01;
+      bl = (print_px(base, p, i * 3 + 2, 2, apply) + 1.0f) * kTo01;
+    } else {
+      r = (base[i * 3 + 0] + 1.0f) * kTo01;
+      g = (base[i * 3 + 1] + 1.0f) * kTo01;
+      bl = (base[i * 3 + 2] + 1.0f) * kTo01;
+    }
+    atomicAdd(&mine[hist_bin(rgb2yuv(r, g, bl).y)], 1u);
+  }
+  __syncthreads();
+  hpart[(((long)b * 2 + z) * gridDim.x + blockIdx.x) * kHistBins + t] =
+      (int)(sh[0][t] + sh[1][t] + sh[2][t] + sh[3][t]);
+}
+
+// interp(dx, dy, x) of brightness_matcher.py:135-162 over 256 knots, dx non-decreasing: the end
+// values outside (dx[0], dx[255]), else the segment whose right knot is the first dx > x
+__device__ __forceinline__ float hist_interp(const float* dx, const float* dy, float x) {
+  if (x <= dx[0]) return dy[0];
+  if (x >= dx[kHistBins - 1]) return dy[kHistBins - 1];
+  int lo = 1, hi = kHistBins - 1;  // dx[0] < x < dx[255]: the first index with dx > x lies in [1, 255]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (dx[mid] > x) hi = mid; else lo = mid + 1;
+  }
+  const int i1 = lo, i0 = lo - 1;
+  return dy[i0] + div_exact((dy[i1] - dy[i0]) * (x - dx[i0]), dx[i1] - dx[i0]);
+}
+
+// one workgroup per image: fold the chunk partials, scan, both CDFs
+// (cdf[k] = f32(c[k] - c[0]) / f32(n - 1)), lut[i] = interp(cdf_t, FS, cdf_s[i]).
+// hist (optional): the folded counts [B,2,256]
+__global__ __launch_bounds__(kHistBins) void k_eot_lut(EotDims d, const int* __restrict__ hpart,
+                                                       int chunks, int* __restrict__ hist,
+                                                       float* __restrict__ lut) {
+  __shared__ int sc[kHistBins];
+  __shared__ float cdf[2][kHistBins];
+  __shared__ float fs[kHistBins];
+  const int b = blockIdx.x, t = threadIdx.x;
+  fs[t] = hist_fs(t);
+  for (int z = 0; z < 2; ++z) {
+    const int* hp = hpart + ((long)b * 2 + z) * chunks * kHistBins;
+    int h = 0;
+    for (int k0 = 0; k0 < chunks; k0 += 16) {  // 16 loads in flight per round (as k_eot_ymean)
+      int v[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) v[u] = hp[(long)min(k0 + u, chunks - 1) * kHistBins + t];
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (k0 + u < chunks) h += v[u];
+    }
+    if (hist) hist[((long)b * 2 + z) * kHistBins + t] = h;
+    __syncthreads();  // the previous side's scan has been read
+    sc[t] = h;
+    __syncthreads();
+    for (int off = 1; off < kHistBins; off <<= 1) {
+      const int a = t >= off ? sc[t - off] : 0;
+      __syncthreads();
+      sc[t] += a;
+      __syncthreads();
+    }
+    const long npx = z == 0 ? (long)d.P * d.P : (long)d.H * d.W;
+    cdf[z][t] = div_exact((float)(sc[t] - sc[0]), (float)(npx - 1));
+  }
+  __syncthreads();
+  lut[(long)b * kHistBins + t] = hist_interp(cdf[1], fs, cdf[0][t]);
+}
+
+// the remap of one pixel's Y through the image's lookup table: the segment (i0, i0 + 1) the
+// reference's interp(FS, lut, y) selects, from floor(255 y) corrected against the knots themselves;
+// inside = FS[0] < y < FS[255] (outside, the end value and no gradient)
+struct HistSeg {
+  int i0;
+  bool inside;
+};
+__device__ __forceinline__ HistSeg hist_seg(float y) {
+  HistSeg s;
+  s.inside = y > hist_fs(0) && y < hist_fs(kHistBins - 1);
+  int i1 = min(max((int)(255.0f * fminf(fmaxf(y, 0.0f), 1.0f)) + 1, 1), kHistBins - 1);
+  while (i1 < kHistBins - 1 && hist_fs(i1) <= y) ++i1;  // the first knot above y
+  while (i1 > 1 && hist_fs(i1 - 1) > y) --i1;
+  s.i0 = i1 - 1;
+  return s;
+}
+__device__ __forceinline__ float hist_remap(const float* lut, float y) {
+  if (y <= hist_fs(0)) return lut[0];
+  if (y >= hist_fs(kHistBins - 1)) return lut[kHistBins - 1];
+  const int i0 = hist_seg(y).i0;
+  const float x0 = hist_fs(i0), x1 = hist_fs(i0 + 1);
+  return lut[i0] + div_exact((lut[i0 + 1] - lut[i0]) * (y - x0), x1 - x0);
+}
+
+// as match_px with the remapped Y (not clipped, brightness_matcher.py:108-113)
+__device__ __forceinline__ void hist_match_px(float p0, float p1, float p2, const float* lut,
+                                              float* o) {
+  Yuv s = rgb2yuv((p0 + 1.0f) * kTo01, (p1 + 1.0f) * kTo01, (p2 + 1.0f) * kTo01);
+  float yp = hist_remap(lut, s.y);
+  float r = yp + 1.13988303f * s.v;
+  float g = yp + -0.394642334f * s.u + -0.58062185f * s.v;
+  float bl = yp + 2.03206185f * s.u;
+  o[0] = fminf(fmaxf(r, 0.0f), 1.0f) * kBack - 1.0f;
+  o[1] = fminf(fmaxf(g, 0.0f), 1.0f) * kBack - 1.0f;
+  o[2] = fminf(fmaxf(bl, 0.0f), 1.0f) * kBack - 1.0f;
+}
+
+__global__ __launch_bounds__(256) void k_eot_hmatch(EotDims d, const float* __restrict__ src,
+                                                    long src_stride, const ImgParams* __restrict__ img,
+                                                    const float* __restrict__ lut, int apply,
+                                                    float* __restrict__ out) {
+  __shared__ float s_lut[kHistBins];
+  const int b = blockIdx.y;
+  s_lut[threadIdx.x] = lut[(long)b * kHistBins + threadIdx.x];
+  __syncthreads();
+  const long npx = (long)d.P * d.P;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npx) return;
+  const ImgParams p = img ? img[b] : ImgParams{};
+  const float* base = src + (long)b * src_stride;
+  float o[3];
+  hist_match_px(print_px(base, p, i * 3, 0, apply), print_px(base, p, i * 3 + 1, 1, apply),
+                print_px(base, p, i * 3 + 2, 2, apply), s_lut, o);
+  float* op = out + ((long)b * npx + i) * 3;
+  op[0] = o[0]; op[1] = o[1]; op[2] = o[2];
+}
+
+size_t eot_hist_part_ints(int B) { return (size_t)B * 2 * kHistChunks * kHistBins; }
+
+void launch_eot_hist_lut(const EotDims& d, const float* patch, const ImgParams* img, const float* tgt,
+                         int* hpart, int* hist, float* lut, bool apply_print, hipStream_t s) {
+  long stride = apply_print ? 0 : (long)d.P * d.P * 3;
+  hipLaunchKernelGGL(k_eot_hist, dim3(kHistChunks, d.B, 2), dim3(256), 0, s, d, patch, stride, img,
+                     tgt, apply_print ? 1 : 0, hpart);
+  PHX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_eot_lut, dim3(d.B), dim3(kHistBins), 0, s, d, hpart, kHistChunks, hist, lut);
+  PHX_LAUNCH_CHECK();
+}
+
+void launch_eot_hist_match(const EotDims& d, const float* patch, const ImgParams* img, const float* tgt,
+                           float* matched, int* hpart, float* lut, bool apply_print, hipStream_t s) {
+  launch_eot_hist_lut(d, patch, img, tgt, hpart, nullptr, lut, apply_print, s);
+  long stride = apply_print ? 0 : (long)d.P * d.P * 3;
+  hipLaunchKernelGGL(k_eot_hmatch, dim3(cdiv((long)d.P * d.P, 256), d.B), dim3(256), 0, s, d, patch,
+                     stride, img, lut, apply_print ? 1 : 0, matched);
   PHX_LAUNCH_CHECK();
 }
 
@@ -1291,6 +1477,96 @@ void launch_eot_patch_bwd(const EotDims& d, const float* patch, const ImgParams*
   hipLaunchKernelGGL(k_eot_patch_grad, dim3(cdiv((long)d.P * d.P, 256)), dim3(256),
                      (size_t)d.B * sizeof(float), s, d, patch,
                      img, ymean, dmatched, dsum, kYChunks, add_tv ? 1 : 0, grad);
+  PHX_LAUNCH_CHECK();
+}
+
+// histogram-matcher backward per pixel.  The histogram op has no gradient, so the lookup table is
+// a constant and Y's gradient is the slope of the segment the forward selected (a pixel on a knot
+// takes the right-hand one; outside (FS[0], FS[255]) it is 0); U, V and the RGB clips as
+// match_bwd_px.  No mean coupling, so no reduction pass.
+__device__ __forceinline__ void hist_match_bwd_px(const float* p, const float* lut, const float* dm,
+                                                  float* dp) {
+  Yuv s = rgb2yuv((p[0] + 1.0f) * kTo01, (p[1] + 1.0f) * kTo01, (p[2] + 1.0f) * kTo01);
+  const HistSeg seg = hist_seg(s.y);
+  float yp, slope = 0.0f;
+  if (seg.inside) {
+    const float x0 = hist_fs(seg.i0), x1 = hist_fs(seg.i0 + 1);
+    const float dl = lut[seg.i0 + 1] - lut[seg.i0];
+    yp = lut[seg.i0] + div_exact(dl * (s.y - x0), x1 - x0);
+    slope = div_exact(dl, x1 - x0);
+  } else {
+    yp = s.y <= hist_fs(0) ? lut[0] : lut[kHistBins - 1];
+  }
+  float rgb[3] = {yp + 1.13988303f * s.v, yp + -0.394642334f * s.u + -0.58062185f * s.v,
+                  yp + 2.03206185f * s.u};
+  float drgb[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    drgb[c] = (rgb[c] >= 0.0f && rgb[c] <= 1.0f) ? dm[c] * kBack : 0.0f;
+  float dyp = drgb[0] + drgb[1] + drgb[2];
+  float du = -0.394642334f * drgb[1] + 2.03206185f * drgb[2];
+  float dv = 1.13988303f * drgb[0] + -0.58062185f * drgb[1];
+  float dy = dyp * slope;
+  dp[0] = (dy * 0.299f + du * -0.14714119f + dv * 0.61497538f) * kTo01;
+  dp[1] = (dy * 0.587f + du * -0.28886916f + dv * -0.51496512f) * kTo01;
+  dp[2] = (dy * 0.114f + du * 0.43601035f + dv * -0.10001026f) * kTo01;
+}
+
+// as k_eot_patch_grad (sum over the images in order, print clip mask, TV).  The images' tables pass
+// through LDS kHistTile at a time, so any batch size runs
+constexpr int kHistTile = 16;
+__global__ __launch_bounds__(256) void k_eot_hpatch_grad(EotDims d, const float* __restrict__ patch,
+                                                         const ImgParams* __restrict__ img,
+                                                         const float* __restrict__ lut,
+                                                         const float* __restrict__ dmatched,
+                                                         int add_tv, float* __restrict__ grad) {
+  __shared__ float s_luts[kHistTile * kHistBins];
+  const long npx = (long)d.P * d.P;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < npx;  // every lane stays for the tile barriers
+  float g[3] = {0.f, 0.f, 0.f};
+  for (int b0 = 0; b0 < d.B; b0 += kHistTile) {
+    const int nb = min(kHistTile, d.B - b0);
+    if (b0) __syncthreads();  // the previous tile's tables have been read
+    for (int k = threadIdx.x; k < nb * kHistBins; k += blockDim.x) s_luts[k] = lut[(long)b0 * kHistBins + k];
+    __syncthreads();
+    if (!live) continue;
+    for (int bb = 0; bb < nb; ++bb) {
+      const int b = b0 + bb;
+      const ImgParams ip = img[b];
+      float p[3], pre[3], dp[3];
+      for (int c = 0; c < 3; ++c) {
+        pre[c] = ip.w[c] * patch[i * 3 + c] + ip.b[c];
+        p[c] = fminf(fmaxf(pre[c], -1.0f), 1.0f);
+      }
+      hist_match_bwd_px(p, s_luts + bb * kHistBins, dmatched + ((long)b * npx + i) * 3, dp);
+      for (int c = 0; c < 3; ++c)
+        if (pre[c] >= -1.0f && pre[c] <= 1.0f) g[c] += dp[c] * ip.w[c];
+    }
+  }
+  if (!live) return;
+  if (add_tv) {
+    const int y = (int)(i / d.P), x = (int)(i % d.P);
+    for (int c = 0; c < 3; ++c) {
+      const float v = patch[i * 3 + c];
+      float t = 0.f;
+      if (y > 0) t += sgnf(v - patch[(i - d.P) * 3 + c]);
+      if (y < d.P - 1) t -= sgnf(patch[(i + d.P) * 3 + c] - v);
+      if (x > 0) t += sgnf(v - patch[(i - 1) * 3 + c]);
+      if (x < d.P - 1) t -= sgnf(patch[(i + 1) * 3 + c] - v);
+      g[c] += 1e-5f * t;
+    }
+  }
+  grad[i * 3 + 0] = g[0];
+  grad[i * 3 + 1] = g[1];
+  grad[i * 3 + 2] = g[2];
+}
+
+void launch_eot_hist_patch_bwd(const EotDims& d, const float* patch, const ImgParams* img,
+                               const float* lut, const float* dmatched, float* grad, bool add_tv,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(k_eot_hpatch_grad, dim3(cdiv((long)d.P * d.P, 256)), dim3(256), 0, s, d, patch,
+                     img, lut, dmatched, add_tv ? 1 : 0, grad);
   PHX_LAUNCH_CHECK();
 }
 

@@ -80,6 +80,13 @@ void launch_eot_match(const EotDims& d, const float* patch, const ImgParams* img
 // brightness matcher over one printed source per image (the defender's Masker: src [B,P,P,3])
 void launch_eot_match_batch(const EotDims& d, const float* src, const ImgParams* img, const float* tgt,
                             float* matched, double* ysum, float* ymean, hipStream_t s);
+// histogram matcher (brightness_matcher.py:76-162), same source conventions as launch_eot_match.
+// hpart: eot_hist_part_ints(B) ints of per-workgroup counts; lut [B,256]; hist (optional) [B,2,256]
+size_t eot_hist_part_ints(int B);
+void launch_eot_hist_lut(const EotDims& d, const float* patch, const ImgParams* img, const float* tgt,
+                         int* hpart, int* hist, float* lut, bool apply_print, hipStream_t s);
+void launch_eot_hist_match(const EotDims& d, const float* patch, const ImgParams* img, const float* tgt,
+                           float* matched, int* hpart, float* lut, bool apply_print, hipStream_t s);
 // per box: pre = resize(matched[b]) + U(-amp, amp) noise + delta  (pre-clip values)
 void launch_eot_resize(const EotDims& d, const float* matched, const BoxPlace* place,
                        const SpanEntry* spans, uint64_t seed, int64_t step, int gimg0,
@@ -101,6 +108,10 @@ long eot_resize_scratch_floats(const EotDims& d);
 void launch_eot_patch_bwd(const EotDims& d, const float* patch, const ImgParams* img,
                           const float* ymean, const float* dmatched, double* dsum, float* grad,
                           bool add_tv, hipStream_t s);
+// the same through the histogram matcher (the lookup table is a constant: segment slopes only)
+void launch_eot_hist_patch_bwd(const EotDims& d, const float* patch, const ImgParams* img,
+                               const float* lut, const float* dmatched, float* grad, bool add_tv,
+                               hipStream_t s);
 // TV value (tf.image.total_variation) into metrics[PHX_M_TV] and 1e-5*TV added to loss
 void launch_tv(const float* patch, int P, double* scratch, float* metrics, bool add_to_loss,
                hipStream_t s);
