@@ -60,7 +60,8 @@ def calc_asr(num, den, coords=4):
 def attack_step(weights, images, patch, scale, boxes=None, seed=0, step=0, gimg0=0,
                 model="efficientdet-d0", image_size=None, add_tv=True, score_thresh=0.5,
                 dtype=torch.float64, training=True, image_grad=False, bn_frozen=False, bf16=False):
-    """Returns dict(loss, grad (NPARAM float64: [patch | scale]), m (per image), patched, ...).
+    """Returns dict(loss, grad (NPARAM float64: [patch | scale]), m (per image), patched, ...,
+    anchor (per image: loss-anchor index, top-1 minus top-2 gap of the kept scores)).
 
     boxes: None -> first-pass soft-NMS boxes (the reference); else a list per image of [n,4]
     arrays used for placement (the first pass still runs, as in the product).
@@ -86,7 +87,7 @@ def attack_step(weights, images, patch, scale, boxes=None, seed=0, step=0, gimg0
     patched = torch.stack(patched)
     cls, box = det(patched)
     scores, classes, dboxes = D.pre_nms(cls, box, image_size, det.cfg["anchor_scale"])
-    m_raw, m, second = [], [], []
+    m_raw, m, second, anchor = [], [], [], []
     for b in range(B):
         keep = torch.as_tensor((classes[b].numpy() == 0)
                                & pp.valid_mask(dboxes[b].numpy().astype(np.float32), image_size, image_size))
@@ -97,6 +98,13 @@ def attack_step(weights, images, patch, scale, boxes=None, seed=0, step=0, gimg0
         second.append((ob[:n], os_[:n]))
         r = _ragged_max(scores[b], keep)
         m_raw.append(r)
+        # the loss anchor (index of the kept maximum in pre_nms order, -1: none kept) and how far the
+        # runner-up is below it (inf with fewer than two kept): diagnostics for argmax stability
+        ks = torch.where(keep, scores[b].detach(), torch.full_like(scores[b].detach(), -np.inf))
+        top = torch.topk(ks, 2)
+        n_keep = int(keep.sum())
+        anchor.append((int(top.indices[0]) if n_keep else -1,
+                       float(top.values[0] - top.values[1]) if n_keep > 1 else float("inf")))
         m.append(torch.where(r >= 0, r, torch.zeros_like(r)))  # tf.maximum(x, 0): grad to x on ties
     m = torch.stack(m)
     scale_losses = (m - scale_t) ** 2
@@ -116,7 +124,8 @@ def attack_step(weights, images, patch, scale, boxes=None, seed=0, step=0, gimg0
     return dict(loss=loss.item(), grad=grad, m=m.detach().numpy(), m_raw=np.array([float(v.detach()) for v in m_raw]),
                 scale_loss=scale_losses.sum().item(), tv=tv.item(), patched=patched.detach().numpy(),
                 places=places, first_pass=fp, second_nms=second, asr_num=num, asr_den=den,
-                nbox=sum(int(p["valid"]) for pl in places for p in pl), det=det, dimg=dimg)
+                nbox=sum(int(p["valid"]) for pl in places for p in pl), det=det, dimg=dimg,
+                anchor=anchor)
 
 
 def adam_clip(params, grad, m, v, lr, t):

@@ -4,7 +4,8 @@ Tolerances (fp32 GPU vs fp64 oracle on identical inputs, weights and EOT draws):
   detector scores            |d| <= 2e-5 absolute (scores are sigmoid outputs in (0,1))
   patched images             |d| <= 1e-4 on >= 99.99 % of values (fill-threshold ties excepted)
   loss                       rel <= 1e-5
-  d patch                    cosine >= 0.99999, ||d - d_ref|| / ||d_ref|| <= 1e-3
+  d patch                    cosine >= 0.99999, ||d - d_ref|| / ||d_ref|| <= 1e-3 (D0 at 128^2, the
+                             case test_gpu_layers.py measures: 1.5e-5)
   d scale                    rel <= 1e-5
   soft-NMS, placement, Adam  exact / float32 round-off
 """
@@ -275,7 +276,9 @@ def test_step_grad_matches_oracle(victim, wdict):
     cos = gp @ rp / (np.linalg.norm(gp) * np.linalg.norm(rp))
     rel = np.linalg.norm(gp - rp) / np.linalg.norm(rp)
     assert cos >= 0.99999, cos
-    assert rel <= 1e-3, rel
+    # 4x the 3.8e-6 measured on an MI355X (test_gpu_layers.py, case A; the fp32 oracle run is 8.1e-6
+    # from fp64 here); the layers between the ends are bounded one by one there
+    assert rel <= 1.5e-5, rel
     mt = torch.empty(2, device="cuda")
     victim.ctx.call("phx_debug_last_maxscores", mt.data_ptr(), None, torch.cuda.current_stream().cuda_stream)
     np.testing.assert_allclose(mt.cpu().numpy(), ref["m_raw"], rtol=1e-5, atol=1e-6)
