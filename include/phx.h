@@ -370,6 +370,25 @@ int phx_def_eval_step(phx_def* d, const float* images, int B, const float* boxes
  * first-pass boxes [B,100,4], counts [B] (int32 bits) */
 enum { PHX_DEF_PATCHED = 0, PHX_DEF_TARGETS = 1, PHX_DEF_UPDATES = 2, PHX_DEF_BOXES = 3, PHX_DEF_COUNTS = 4 };
 int phx_def_debug(phx_def* d, int what, float* dst, size_t nfloats, void* stream);
+/* Read-only tap of a tensor the U-Net forward of the last step (training or evaluation) stored; the
+ * backward reads these and leaves them as they are.  Copies the named tensor, NHWC float32
+ * [B,h,w,C], to dst (any memory, nfloats >= its size); nothing but the copy is launched.  Names, in
+ * program order (i = 0..3; the encoder level i works at S >> i, decoder i at S >> (3 - i)):
+ *   conv<i>/y1, /a1, /y2, /a2     encoder block i: y* = the 3x3 conv outputs with bias, before BN;
+ *                                 a* = leaky_relu(BN(y*))
+ *   conv<i>/pool                  max-pool 2x2 of a2, after Dropout in training [B,h/2,w/2,C]
+ *   conv4/y1, /a1, /y2, /a2       the bottleneck block
+ *   deconv<i>/up                  the transposed conv's output with bias
+ *   deconv<i>/att_g, /att_x       the attention's 1x1 conv outputs (of up / of the skip) with bias,
+ *                                 before their BN
+ *   deconv<i>/att_s               leaky_relu(BN1(att_g) + BN2(att_x))
+ *   deconv<i>/att_t               the 1-channel 1x1 conv of att_s with bias, before bn3 [B,h,w,1]
+ *   deconv<i>/cat                 concat(up, skip * sigmoid(bn3(att_t))), after Dropout in training
+ *   deconv<i>/convblock/y1, /a1, /y2, /a2   the decoder's conv block
+ *   updates                       2 * tanh(output conv) [B,S,S,3]
+ * PHX_EINVAL: unknown name; PHX_ESTATE: no U-Net forward has run since the workspace was (re)built (a
+ * new batch size rebuilds it); PHX_ECAP: destination too small. */
+int phx_def_debug_tap(phx_def* d, const char* name, float* dst, size_t nfloats, void* stream);
 /* Keras Adam without constraints (the defender's optimizer, defender_train.py:35) */
 int phx_adam(float* params, const float* grad, float* m, float* v, int64_t n, float lr, int64_t t, void* stream);
 

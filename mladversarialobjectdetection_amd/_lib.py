@@ -121,6 +121,7 @@ _SIGS = [
      [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_int64, c_int, c_void_p]),
     ("phx_def_debug", c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    ("phx_def_debug_tap", c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]),
     ("phx_adam", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p]),
 ]
 

@@ -115,6 +115,7 @@ struct phx_def {
   }
   // per batch-size workspace
   int wsB = 0;
+  int fwdB = 0;  // batch size of the last U-Net forward into this workspace (0: none yet; phx_def_debug_tap)
   std::vector<DBuf> owned;
   template <class T>
   T* alloc(size_t n) {
@@ -306,6 +307,7 @@ void phx_def::workspace(int B) {
   owned.clear();
   ws_bytes = 0;
   wsB = B;
+  fwdB = 0;
   const int S_ = S;
   auto F = [&](size_t n) {
     ws_bytes += n * 4;
@@ -504,6 +506,7 @@ void phx_def::unet_forward(int B, const float* W, bool train, int64_t stp, int g
   const UConv& oc = convs[out_conv];
   DScope g(victim, "unet_other", 2.0 * Mf * 3 * oc.ci, 4.0 * Mf * (oc.ci + 9), s);
   un_out_loss(x, W + oc.w, W + oc.b, mask, upd, dz, lpart, loss, Mf, (long)S * S, oc.ci, s);
+  fwdB = B;
 }
 
 // derived GEMM operands of this step's weights
@@ -905,6 +908,54 @@ int phx_def_debug(phx_def* d, int what, float* dst, size_t n, void* stream) {
     default: throw std::invalid_argument("phx_def_debug: unknown tensor");
   }
   if (n < have) throw std::out_of_range("phx_def_debug: destination too small");
+  PHX_HIP(hipMemcpyAsync(dst, src, have * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+  return PHX_OK;
+  DEF_CATCH(d)
+}
+
+int phx_def_debug_tap(phx_def* d, const char* name, float* dst, size_t nfloats, void* stream) {
+  if (!d || !name || !dst) return PHX_EINVAL;
+  DEF_TRY
+  // (a rebuilt workspace holds nothing until a forward has written it)
+  if (d->wsB == 0 || d->fwdB != d->wsB) throw std::logic_error("phx_def_debug_tap: no U-Net forward has run");
+  // every tensor the U-Net forward stores (the backward reads them as const), by name
+  const std::string want = name;
+  const float* src = nullptr;
+  size_t have = 0;
+  auto offer = [&](const std::string& n, const float* p, long M, int C) {
+    if (n == want) { src = p; have = (size_t)M * C; }
+  };
+  const int B = d->wsB, S = d->S;
+  for (int i = 0; i < 4; ++i) {
+    const int H = S >> i, n = d->convs[d->enc[i].c1].co;
+    const long M = (long)B * H * H;
+    const std::string p = "conv" + std::to_string(i) + "/";
+    const phx_def::EncT& e = d->et[i];
+    offer(p + "y1", e.y1, M, n); offer(p + "a1", e.a1, M, n); offer(p + "y2", e.y2, M, n); offer(p + "a2", e.a2, M, n);
+    offer(p + "pool", e.p, M / 4, n);
+  }
+  {
+    const int H = S >> 4, n = d->convs[d->c4.c1].co;
+    const long M = (long)B * H * H;
+    const phx_def::C4T& c = d->c4t;
+    offer("conv4/y1", c.y1, M, n); offer("conv4/a1", c.a1, M, n); offer("conv4/y2", c.y2, M, n);
+    offer("conv4/a2", c.a2, M, n);
+  }
+  for (int i = 0; i < 4; ++i) {
+    const int H = S >> (3 - i), n = d->convs[d->dec[i].up].co;
+    const long M = (long)B * H * H;
+    const std::string p = "deconv" + std::to_string(i) + "/";
+    const phx_def::DecT& t = d->dt[i];
+    offer(p + "up", t.up, M, n); offer(p + "att_g", t.g, M, n); offer(p + "att_x", t.xs, M, n);
+    offer(p + "att_s", t.s, M, n); offer(p + "att_t", t.t, M, 1); offer(p + "cat", t.cat, M, 2 * n);
+    offer(p + "convblock/y1", t.y1, M, n); offer(p + "convblock/a1", t.a1, M, n);
+    offer(p + "convblock/y2", t.y2, M, n); offer(p + "convblock/a2", t.a2, M, n);
+  }
+  offer("updates", d->upd, (long)B * S * S, 3);
+  if (!src) throw std::invalid_argument("phx_def_debug_tap: no tensor named " + want);
+  if (nfloats < have)
+    throw std::out_of_range("phx_def_debug_tap: destination too small (the tensor has " + std::to_string(have) +
+                            " elements)");
   PHX_HIP(hipMemcpyAsync(dst, src, have * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
   return PHX_OK;
   DEF_CATCH(d)

@@ -128,6 +128,28 @@ def init_unet_params(manifest: dict, seed: int = 0) -> np.ndarray:
     return out
 
 
+def unet_tap_shapes(S: int, B: int, nf: int = 8) -> dict:
+    """{name: NHWC shape} of the tensors phx_def_debug_tap names (include/phx.h), in program order."""
+    out = {}
+    for i in range(4):
+        H, n = S >> i, nf << i
+        for t in ("y1", "a1", "y2", "a2"):
+            out[f"conv{i}/{t}"] = (B, H, H, n)
+        out[f"conv{i}/pool"] = (B, H // 2, H // 2, n)
+    for t in ("y1", "a1", "y2", "a2"):
+        out[f"conv4/{t}"] = (B, S >> 4, S >> 4, nf * 16)
+    for i in range(4):
+        H, n = S >> (3 - i), nf << (3 - i)
+        for t in ("up", "att_g", "att_x", "att_s"):
+            out[f"deconv{i}/{t}"] = (B, H, H, n)
+        out[f"deconv{i}/att_t"] = (B, H, H, 1)
+        out[f"deconv{i}/cat"] = (B, H, H, 2 * n)
+        for t in ("y1", "a1", "y2", "a2"):
+            out[f"deconv{i}/convblock/{t}"] = (B, H, H, n)
+    out["updates"] = (B, S, S, 3)
+    return out
+
+
 class PatchAttackDefender:
     """attack_detection.PatchAttackDefender (training path): the protege is frozen (inference BN),
     the trainable variables are the U-Net's."""
@@ -294,6 +316,13 @@ class PatchAttackDefender:
         self.handle.call("phx_def_debug", int(what), out.data_ptr(), out.numel(), _stream())
         if what == _lib.DEF_COUNTS:
             return out.view(torch.int32)
+        return out
+
+    def debug_tap(self, name: str, B: int):
+        """One stored tensor of the last step's U-Net forward (phx_def_debug_tap), NHWC."""
+        shape = unet_tap_shapes(self.protege_model.ctx.image_size, B)[name]
+        out = torch.empty(shape, device=self.params.device)
+        self.handle.call("phx_def_debug_tap", name.encode(), out.data_ptr(), out.numel(), _stream())
         return out
 
     def save_weights(self, dirpath, **kwargs):

@@ -115,7 +115,13 @@ def dropout_mask(shape_nhwc, layer, seed, step, gimg0):
 
 
 class UNet:
-    def __init__(self, params: dict, moving: dict, dtype=torch.float64, training=True, seed=0, step=0, gimg0=0):
+    """taps (optional dict, off by default): filled by a call with every tensor the product's forward
+    stores, under the names of phx_def_debug_tap (include/phx.h) in program order — torch tensors,
+    NCHW, attached to the graph; `nhwc_taps` returns them as NHWC numpy arrays.  bn_stats then holds
+    {BN name: (batch mean, batch variance)} (training mode)."""
+
+    def __init__(self, params: dict, moving: dict, dtype=torch.float64, training=True, seed=0, step=0, gimg0=0,
+                 taps=None):
         self.p = {k: torch.as_tensor(np.asarray(v, np.float64), dtype=dtype) for k, v in params.items()}
         for v in self.p.values():
             v.requires_grad_(True)
@@ -123,6 +129,13 @@ class UNet:
                        for k, (m, v) in moving.items()}
         self.dtype, self.training = dtype, training
         self.seed, self.step, self.gimg0 = seed, step, gimg0
+        self.taps = taps
+        self.bn_stats = {}
+
+    def tap(self, name, x):
+        if self.taps is not None:
+            self.taps[name] = x
+        return x
 
     def conv(self, x, name, k):
         w = self.p[f"{name}/kernel"].permute(3, 2, 0, 1)  # [k,k,ci,co] -> [co,ci,k,k]
@@ -143,15 +156,23 @@ class UNet:
             mm, mv = self.moving[name]
             uvar = var.detach().numpy() * n / max(n - 1, 1)
             self.moving[name] = (mm - (mm - mean.detach().numpy()) * 0.01, mv - (mv - uvar) * 0.01)
+            if self.taps is not None:
+                self.bn_stats[name] = (mean.detach().numpy().copy(), var.detach().numpy().copy())
         else:
             mean = torch.as_tensor(self.moving[name][0], dtype=x.dtype)
             var = torch.as_tensor(self.moving[name][1], dtype=x.dtype)
         inv = 1.0 / torch.sqrt(var + 1e-3)
+        return self.bn_affine(x, mean, inv, g, b, name)
+
+    def bn_affine(self, x, mean, inv, g, b, name):
         return (x - mean[None, :, None, None]) * (inv * g)[None, :, None, None] + b[None, :, None, None]
 
     @staticmethod
     def leaky(x):
         return F.leaky_relu(x, 0.2)
+
+    def bn_act(self, x, name):
+        return self.leaky(self.bn(x, name))
 
     def dropout(self, x, layer):
         if not self.training:
@@ -159,18 +180,28 @@ class UNet:
         keep = dropout_mask((x.shape[0], x.shape[2], x.shape[3], x.shape[1]), layer, self.seed, self.step,
                             self.gimg0)
         keep_t = torch.as_tensor(keep.transpose(0, 3, 1, 2), dtype=x.dtype)
-        return x * 1.25 * keep_t
+        return x * self.dropout_scale(layer) * keep_t
+
+    def dropout_scale(self, layer):
+        return 1.25  # 1 / (1 - DROP)
 
     def block(self, x, name):
-        x = self.leaky(self.bn(self.conv(x, f"{name}/cnv1", 3), f"{name}/bn1"))
-        return self.leaky(self.bn(self.conv(x, f"{name}/cnv2", 3), f"{name}/bn2"))
+        x = self.tap(f"{name}/y1", self.conv(x, f"{name}/cnv1", 3))
+        x = self.tap(f"{name}/a1", self.bn_act(x, f"{name}/bn1"))
+        x = self.tap(f"{name}/y2", self.conv(x, f"{name}/cnv2", 3))
+        return self.tap(f"{name}/a2", self.bn_act(x, f"{name}/bn2"))
+
+    def gate(self, skip, a, name):
+        return skip * a
 
     def attention(self, up, skip, name):
-        g = self.bn(self.conv(up, f"{name}/cnv1", 1), f"{name}/bn1")
-        x = self.bn(self.conv(skip, f"{name}/cnv2", 1), f"{name}/bn2")
-        s = self.leaky(g + x)
-        a = torch.sigmoid(self.bn(self.conv(s, f"{name}/conv3", 1), f"{name}/bn3"))
-        return skip * a
+        top = name.split("/")[0]
+        g = self.bn(self.tap(f"{top}/att_g", self.conv(up, f"{name}/cnv1", 1)), f"{name}/bn1")
+        x = self.bn(self.tap(f"{top}/att_x", self.conv(skip, f"{name}/cnv2", 1)), f"{name}/bn2")
+        s = self.tap(f"{top}/att_s", self.leaky(g + x))
+        t = self.tap(f"{top}/att_t", self.conv(s, f"{name}/conv3", 1))
+        a = torch.sigmoid(self.bn(t, f"{name}/bn3"))
+        return self.gate(skip, a, name)
 
     def __call__(self, images_nhwc):
         x = images_nhwc.permute(0, 3, 1, 2)
@@ -178,15 +209,21 @@ class UNet:
         for i in range(4):
             x = self.block(x, f"conv{i}")
             encs.append(x)
-            x = self.dropout(F.max_pool2d(x, 2), i)
+            x = self.tap(f"conv{i}/pool", self.dropout(F.max_pool2d(x, 2), i))
         x = self.block(x, "conv4")
         for i, enc in enumerate(encs[::-1]):
-            up = self.tconv(x, f"deconv{i}/cnv")
+            up = self.tap(f"deconv{i}/up", self.tconv(x, f"deconv{i}/cnv"))
             skip = self.attention(up, enc, f"deconv{i}/attention")
-            x = self.dropout(torch.cat([up, skip], 1), 4 + i)
+            x = self.tap(f"deconv{i}/cat", self.dropout(torch.cat([up, skip], 1), 4 + i))
             x = self.block(x, f"deconv{i}/convblock")
         out = torch.tanh(self.conv(x, "output", 1))
         return out.permute(0, 2, 3, 1)
+
+
+def nhwc_taps(taps):
+    """a UNet's taps as NHWC numpy arrays (`updates`, recorded by the step, is NHWC already)"""
+    return {k: (v.detach() if k == "updates" else v.detach().permute(0, 2, 3, 1)).contiguous().numpy()
+            for k, v in taps.items()}
 
 
 # ------------------------------------------------------------------------------------------
@@ -347,11 +384,14 @@ def first_pass(det, images_t, image_size, score_thresh=0.5, filter_thresh=None):
 
 
 def defender_step(unet_params, moving, images, boxes=None, victim_weights=None, model="efficientdet-d0",
-                  image_size=None, seed=0, step=0, gimg0=0, score_thresh=0.5, masked=None, dtype=torch.float64):
+                  image_size=None, seed=0, step=0, gimg0=0, score_thresh=0.5, masked=None, dtype=torch.float64,
+                  taps=None, unet=None):
     """PatchAttackDefender.call(images, training=True): dict(loss, grad (flat, manifest order),
     patched, targets, updates, moving (updated), first_pass).  masked = (patched, targets) skips the
     Masker (the U-Net parity test feeds the product's own Masker outputs).  dtype: the detector's and
-    U-Net's arithmetic (fp64 for parity; fp32 is the CPU baseline the defender bench times)."""
+    U-Net's arithmetic (fp64 for parity; fp32 is the CPU baseline the defender bench times).  taps: a
+    dict to fill with the U-Net's stored tensors (UNet.taps, NHWC numpy on return, `updates` last); the
+    result then also holds taps and bn_stats.  unet: the U-Net class (default UNet)."""
     layout, bns = unet_layout()
     images = np.asarray(images, np.float32)
     fp = None
@@ -364,15 +404,20 @@ def defender_step(unet_params, moving, images, boxes=None, victim_weights=None, 
         patched, targets = (np.asarray(a, np.float64) for a in masked)
     else:
         patched, targets = masker(images, boxes, seed, step, gimg0)
-    net = UNet(unpack(unet_params, layout), moving, dtype=dtype, seed=seed, step=step, gimg0=gimg0)
-    upd = 2.0 * net(torch.as_tensor(patched, dtype=dtype))
+    net = (unet or UNet)(unpack(unet_params, layout), moving, dtype=dtype, seed=seed, step=step, gimg0=gimg0,
+                         taps=taps)
+    upd = net.tap("updates", 2.0 * net(torch.as_tensor(patched, dtype=dtype)))
     t = torch.as_tensor(targets, dtype=dtype)
     B = images.shape[0]
     loss = ((t.reshape(B, -1) - upd.reshape(B, -1)) ** 2).mean(dim=1).sum()
     grads = torch.autograd.grad(loss, [net.p[n] for n, _ in layout])
     grad = np.concatenate([g.detach().numpy().reshape(-1) for g in grads])
-    return dict(loss=loss.item(), grad=grad, patched=patched, targets=targets, updates=upd.detach().numpy(),
-                moving=net.moving, first_pass=fp, boxes=boxes)
+    out = dict(loss=loss.item(), grad=grad, patched=patched, targets=targets, updates=upd.detach().numpy(),
+               moving=net.moving, first_pass=fp, boxes=boxes)
+    if taps is not None:
+        taps.update(nhwc_taps(taps))
+        out.update(taps=taps, bn_stats=net.bn_stats)
+    return out
 
 
 def adam(params, grad, m, v, lr, t):
@@ -388,18 +433,20 @@ def adam(params, grad, m, v, lr, t):
 
 def defender_eval(unet_params, moving, images, eval_patch, eval_scale, victim_weights, boxes=None,
                   model="efficientdet-d0", image_size=None, seed=0, step=0, gimg0=0, score_thresh=0.5,
-                  masked=None):
+                  masked=None, dtype=torch.float64, taps=None, unet=None):
     """PatchAttackDefender.call(images, training=False) (attack_detection.py:168-198) as test_step
     runs it: first pass (unless `boxes`), the Masker's evaluation branch with the attacker's patch,
     the second detector pass odet_model(images, score_thresh=0.) (soft-NMS at 0.001, valid filter at
     the config's score_thresh), updates = 2 * U-Net(images, training=False) and the loss.  Returns
     dict(loss, patched, targets, updates, second=[(boxes, scores)] per image, boxes).  masked =
     (patched, targets) skips the first pass and the Masker (the U-Net check feeds the product's own);
-    victim_weights None skips the second pass (second = None)."""
+    victim_weights None skips the second pass (second = None) and builds no detector.  dtype: the
+    U-Net's arithmetic; taps / unet as defender_step's (the result then holds taps)."""
     layout, _ = unet_layout()
     images = np.asarray(images, np.float32)
     image_size = image_size or images.shape[1]
-    det = D.Detector(victim_weights, model, image_size, training=False)
+    det = None if victim_weights is None and masked is not None else D.Detector(victim_weights, model, image_size,
+                                                                                training=False)
     if masked is not None:
         patched, targets = (np.asarray(a, np.float64) for a in masked)
     else:
@@ -409,11 +456,15 @@ def defender_eval(unet_params, moving, images, eval_patch, eval_scale, victim_we
         patched, targets = masker_eval(images, boxes, eval_patch, eval_scale, seed, step, gimg0)
     second = None if victim_weights is None else first_pass(det, torch.as_tensor(patched), image_size, 0.0,
                                                              filter_thresh=score_thresh)
-    net = UNet(unpack(unet_params, layout), moving, training=False, seed=seed, step=step, gimg0=gimg0)
+    net = (unet or UNet)(unpack(unet_params, layout), moving, dtype=dtype, training=False, seed=seed, step=step,
+                         gimg0=gimg0, taps=taps)
     with torch.no_grad():
-        upd = 2.0 * net(torch.as_tensor(patched))
-    t = torch.as_tensor(targets)
+        upd = net.tap("updates", 2.0 * net(torch.as_tensor(patched, dtype=dtype)))
+    t = torch.as_tensor(targets, dtype=dtype)
     B = images.shape[0]
     loss = ((t.reshape(B, -1) - upd.reshape(B, -1)) ** 2).mean(dim=1).sum()
-    return dict(loss=loss.item(), patched=patched, targets=targets, updates=upd.numpy(), second=second,
-                boxes=boxes)
+    out = dict(loss=loss.item(), patched=patched, targets=targets, updates=upd.numpy(), second=second, boxes=boxes)
+    if taps is not None:
+        taps.update(nhwc_taps(taps))
+        out["taps"] = taps
+    return out

@@ -16,16 +16,22 @@ protege's layers are frozen, attack_detection.py:46-47) and the person prior (pe
 first pass yields boxes.
 Tolerances: first-pass counts / boxes exact; patched pixels and targets 99.99 % within 1e-4 (the
 bilinear rotation's floor boundaries, as the attacker's EOT test); loss rel <= 1e-5; gradient cosine
->= 0.99999 and |d|/|ref| <= 1e-3 overall; moving statistics rel <= 1e-5.
+>= 0.99999 and |d|/|ref| overall <= 4x the measured value (or the fp32 oracle's own deviation where
+that is smaller); every stored tensor, every variable's gradient and the analytically-zero bias
+gradients within unet_parity.py's multiples of the fp32 oracle's own deviation; moving statistics rtol
+1e-4.
 """
 import numpy as np
 import pytest
 import torch
 
+import unet_parity as UP
+
 pytestmark = pytest.mark.gpu
 
 S = 256
 B = 2
+MEASURED_REL = 3.081e-4  # test_unet_step_matches_oracle's overall ||g - g64|| / ||g64|| on an MI355X
 
 
 def _stream():
@@ -111,7 +117,6 @@ def test_masker_matches_oracle(defender):
 
 
 def test_unet_step_matches_oracle(defender):
-    from oracle import defender as DF
     imgs = _images(3)
     mv0 = _moving0(defender)
     params = defender.params.cpu().numpy().copy()
@@ -123,19 +128,24 @@ def test_unet_step_matches_oracle(defender):
     patched = defender.debug(0, B).cpu().numpy()
     targets = defender.debug(1, B).cpu().numpy()
     upd = defender.debug(2, B).cpu().numpy()
-    ref = DF.defender_step(params, mv0, imgs, boxes=_boxes(), seed=9, step=5, masked=(patched, targets))
+    fwd = UP.gpu_taps(defender, B)
+    torch.set_num_threads(16)
+    full = UP.reference(params, mv0, patched, targets, seed=9, step=5)  # the oracle in fp64 and in fp32
+    ref = full.r64
     assert abs(loss - ref["loss"]) <= 1e-5 * abs(ref["loss"])
     assert np.abs(upd - ref["updates"]).max() <= 1e-4
-    rg = ref["grad"]
-    cos = g @ rg / (np.linalg.norm(g) * np.linalg.norm(rg))
+    rel, cos = UP.overall(g, full)
+    print(f"overall rel {rel:.3e} (fp32 oracle {full.overall32:.3e}) cos {cos:.9f}")
     assert cos >= 0.99999, cos
-    assert np.linalg.norm(g - rg) <= 1e-3 * np.linalg.norm(rg)
-    # per variable: every variable's gradient is produced (no stale or missing writes)
-    for p in defender.manifest["params"]:
-        sl = slice(p["offset"], p["offset"] + int(np.prod(p["shape"])))
-        nr = np.linalg.norm(rg[sl])
-        if nr > 1e-6:
-            assert np.linalg.norm(g[sl] - rg[sl]) <= 2e-2 * nr, p["name"]
+    # 4x the rel measured on an MI355X, or the fp32 oracle's own where that is smaller, and never above
+    # the 1e-3 this test held before
+    assert rel <= min(1e-3, 4 * MEASURED_REL, full.overall32), (rel, full.overall32)
+    # per tap and per variable, within a multiple of the fp32 oracle's own deviation (unet_parity.py):
+    # the 100 variables with a gradient, and the 30 analytically-zero biases against their kernels
+    rep = UP.sweep(full, fwd, g, var_cap=2e-2)  # (and never above the 2e-2 this test held before)
+    print(rep.table())
+    rep.check()
+    assert rep.counts() == dict(fwd=UP.N_FWD, var=UP.N_VAR, zero=UP.N_ZERO)
     mv = defender.moving_statistics()
     for b in defender.manifest["bn"]:
         rm, rv = ref["moving"][b["name"]]

@@ -3,7 +3,8 @@ only at 256^2).  The U-Net (generator.py:17-277) then has its full five-level de
 128 / 64 / 32 pixels, the levels the 256^2 case never reaches.
 
   * B = 2 against the fp64 oracle (oracle/defender.py): Masker pixels, loss, every variable's
-    gradient, moving statistics — the tolerances of tests/test_gpu_defender.py;
+    gradient and stored tensor (unet_parity.py's bounds), moving statistics — the tolerances of
+    tests/test_gpu_defender.py;
   * B = 8 (C5's per-GPU share of 64 images over 8 GPUs): bit-identical on rerun, and the loss the
     library reports equals sum_b mean((t - u)^2) recomputed in fp64 from its own targets and
     U-Net updates (2 * unet(x), attack_detection.py:189-193), a size-independent consistency check.
@@ -12,9 +13,12 @@ import numpy as np
 import pytest
 import torch
 
+import unet_parity as UP
+
 pytestmark = pytest.mark.gpu
 
 S = 512
+MEASURED_REL = 3.486e-4  # test_defender_512_step_matches_oracle's overall ||g - g64|| / ||g64|| on an MI355X
 
 
 def _victim(B):
@@ -57,23 +61,27 @@ def test_defender_512_step_matches_oracle():
     patched = d.debug(0, B).cpu().numpy()
     targets = d.debug(1, B).cpu().numpy()
     upd = d.debug(2, B).cpu().numpy()
+    fwd = UP.gpu_taps(d, B)
     torch.set_num_threads(16)
     rp, rt = DF.masker(imgs, _boxes(), 9, 5, 0)
     for got, ref in ((patched, rp), (targets, rt)):
         dd = np.abs(got - ref)
         assert (dd <= 1e-4).mean() >= 0.9999, f"{(dd > 1e-4).mean():.2e} off, max {dd.max():.3e}"
-    ref = DF.defender_step(params, mv0, imgs, boxes=_boxes(), seed=9, step=5, masked=(patched, targets))
+    full = UP.reference(params, mv0, patched, targets, seed=9, step=5)  # the oracle in fp64 and in fp32
+    ref = full.r64
     assert abs(loss - ref["loss"]) <= 1e-5 * abs(ref["loss"])
     assert np.abs(upd - ref["updates"]).max() <= 1e-4
-    rg = ref["grad"]
-    cos = g @ rg / (np.linalg.norm(g) * np.linalg.norm(rg))
+    rel, cos = UP.overall(g, full)
+    print(f"overall rel {rel:.3e} (fp32 oracle {full.overall32:.3e}) cos {cos:.9f}")
     assert cos >= 0.99999, cos
-    assert np.linalg.norm(g - rg) <= 1e-3 * np.linalg.norm(rg)
-    for p in d.manifest["params"]:
-        sl = slice(p["offset"], p["offset"] + int(np.prod(p["shape"])))
-        nr = np.linalg.norm(rg[sl])
-        if nr > 1e-6:
-            assert np.linalg.norm(g[sl] - rg[sl]) <= 2e-2 * nr, p["name"]
+    # 4x the rel measured on an MI355X, or the fp32 oracle's own where that is smaller, and never above
+    # the 1e-3 this test held before
+    assert rel <= min(1e-3, 4 * MEASURED_REL, full.overall32), (rel, full.overall32)
+    # per tap and per variable, within a multiple of the fp32 oracle's own deviation (unet_parity.py)
+    rep = UP.sweep(full, fwd, g, var_cap=2e-2)  # (and never above the 2e-2 this test held before)
+    print(rep.table())
+    rep.check()
+    assert rep.counts() == dict(fwd=UP.N_FWD, var=UP.N_VAR, zero=UP.N_ZERO)
     mv = d.moving_statistics()
     for b in d.manifest["bn"]:
         rm, rv = ref["moving"][b["name"]]
