@@ -15,6 +15,15 @@ def build(jobs: int = 8, verbose: bool = False) -> str:
         sys.stdout.write(r.stdout)
     if r.returncode != 0:
         raise RuntimeError("libphx build failed")
+    # the GEMM kernel parity checker links against the library (tests/test_gpu_gemm_kernels.py runs it)
+    kern = os.path.join(os.path.dirname(HERE), "tests", "kernels")
+    if os.path.isfile(os.path.join(kern, "Makefile")):
+        r = subprocess.run(["make", "-C", kern, f"-j{min(jobs, 16)}"], env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True)
+        if verbose or r.returncode != 0:
+            sys.stdout.write(r.stdout)
+        if r.returncode != 0:
+            raise RuntimeError("tests/kernels build failed")
     return os.path.join(HERE, "libphx.so")
 
 
