@@ -179,6 +179,19 @@ void launch_dw_fwd_fused(const FuseView& fv, const float* w, float* y, int B, in
                          int Wo, int k, int stride, int pt, int pl, hipStream_t s);
 void launch_dw_bwd_group(const DwSeg* segs, int n, int B, int C, const float* w, int k, int stride,
                          hipStream_t s, int* nps);
+// The tile geometry the launchers above plan (host only, read-only: tests/kernels/conv_parity prints it
+// to hold its case table to the edges).  bwd: the data gradient's plan (tiles over the conv input).
+struct DwTileInfo {
+  int lcg, rpt, otw, oth, nrg, rin, cin, tiles_x, ntiles, ncg;
+  int small;  // dw_fused_tile_info: the launch takes the one-row, one-quad plan (few workgroups)
+  long wgs;   // dw_fused_tile_info: B * ntiles * ncg of the ordinary plan, which decides `small`
+};
+DwTileInfo dw_tile_info(int H, int W, int C, int Ho, int Wo, int pt, int pl, int k, int stride, bool bwd);
+DwTileInfo dw_fused_tile_info(int B, int H, int W, int C, int Ho, int Wo, int pt, int pl);
+struct SepTileInfo {
+  int tw, th, tiles_x, ntiles;
+};
+SepTileInfo sep_tile_info(int H, int W);
 void launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s);
 
 // ---- normalisation / elementwise (kernels_norm.hip) ---------------------------------------

@@ -548,6 +548,19 @@ int launch_dw_fwd(InX x, const float* w, float* y, int B, int H, int W, int C, i
   return B * grp.s[0].g.ntiles;
 }
 
+// The small BiFPN levels (8x8 .. 32x32) give a few hundred workgroups or less, each walking its
+// staging batches and four output rows in turn: there one channel quad and one output row per lane
+// spread the same work over up to 16x the workgroups.  Each output keeps its tap order (rows, then
+// columns), and this launch has no statistics, so the outputs are bit-identical.
+// g: the ordinary (four rows per lane) plan of the launch
+static bool dw_fused_small(int B, const DwGeom& g) {
+  static const long small_below = [] {
+    const char* e = std::getenv("PHX_DW_FUSE_SMALL");  // workgroup count below which (0: off)
+    return e ? std::atol(e) : 512L;
+  }();
+  return (long)B * g.ntiles * g.ncg < small_below;
+}
+
 // BiFPN node: depthwise conv of the node's fuse, computed on load (3x3 stride 1 only)
 void launch_dw_fwd_fused(const FuseView& fv, const float* w, float* y, int B, int H, int W, int C, int Ho,
                          int Wo, int k, int stride, int pt, int pl, hipStream_t s) {
@@ -556,16 +569,7 @@ void launch_dw_fwd_fused(const FuseView& fv, const float* w, float* y, int B, in
   DwFwdGroup<1, FuseView> grp{};
   grp.w = w;
   grp.s[0] = DwFwdSegT<FuseView>{fv, y, dw_plan(H, W, C, Ho, Wo, pt, pl, k, stride, 4, false), StatSink{}};
-  // The small BiFPN levels (8x8 .. 32x32) give a few hundred workgroups or less, each walking its
-  // staging batches and four output rows in turn: there one channel quad and one output row per lane
-  // spread the same work over up to 16x the workgroups.  Each output keeps its tap order (rows, then
-  // columns), and this launch has no statistics, so the outputs are bit-identical.
-  static const long small_below = [] {
-    const char* e = std::getenv("PHX_DW_FUSE_SMALL");  // workgroup count below which (0: off)
-    return e ? std::atol(e) : 512L;
-  }();
-  const long wgs = (long)B * grp.s[0].g.ntiles * grp.s[0].g.ncg;
-  if (wgs < small_below) {
+  if (dw_fused_small(B, grp.s[0].g)) {
     grp.s[0].g = dw_plan(H, W, C, Ho, Wo, pt, pl, k, stride, 1, false, 0);
     if (dw_lds(grp.s[0].g, k) > 160 * 1024) throw std::runtime_error("dw: LDS window too large");
     dw_fwd_go<3, 1, 1, 1, FuseView>(grp, 1, B, false, s);
@@ -664,6 +668,25 @@ void launch_dw_bwd_group(const DwSeg* segs, int n, int B, int C, const float* w,
     nps[i] = grp.s[i].gs.P;
   }
   dw_bwd_dispatch(grp, n, B, gsums, k, stride, s);
+}
+
+// ---- the plans, for the kernel parity checker --------------------------------------------------
+static DwTileInfo dw_info_of(const DwGeom& g, int rpt) {
+  return DwTileInfo{g.lcg, rpt, g.otw, g.oth, g.nrg, g.rin, g.cin, g.tiles_x, g.ntiles, g.ncg, 0, 0};
+}
+
+DwTileInfo dw_tile_info(int H, int W, int C, int Ho, int Wo, int pt, int pl, int k, int stride, bool bwd) {
+  const int rpt = bwd ? 4 : dw_rpt_fwd(stride);
+  return dw_info_of(dw_plan(H, W, C, Ho, Wo, pt, pl, k, stride, rpt, bwd), rpt);
+}
+
+DwTileInfo dw_fused_tile_info(int B, int H, int W, int C, int Ho, int Wo, int pt, int pl) {
+  const DwGeom g = dw_plan(H, W, C, Ho, Wo, pt, pl, 3, 1, 4, false);
+  const bool small = dw_fused_small(B, g);
+  DwTileInfo t = small ? dw_info_of(dw_plan(H, W, C, Ho, Wo, pt, pl, 3, 1, 1, false, 0), 1) : dw_info_of(g, 4);
+  t.small = small ? 1 : 0;
+  t.wgs = (long)B * g.ntiles * g.ncg;
+  return t;
 }
 
 }  // namespace phx

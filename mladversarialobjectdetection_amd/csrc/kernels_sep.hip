@@ -658,6 +658,11 @@ bool sep_supported(int C, int N, bool bf16) { return !bf16 && C == 64 && N >= 1 
 
 int sep_stat_partials(int B, int H, int W) { return B * sep_geom(H, W, 0).ntiles; }
 
+SepTileInfo sep_tile_info(int H, int W) {
+  const SepGeom g = sep_geom(H, W, 0);
+  return SepTileInfo{1 << g.ltw, g.th, g.tiles_x, g.ntiles};
+}
+
 void launch_sep_fwd(const SepMember* mem, int n, int B, int C, int N, const float* wd, const float* bt,
                     const float* bias, hipStream_t s, int* nps) {
   if (n < 1 || n > kMaxSeg) throw std::invalid_argument("sep: bad member count");

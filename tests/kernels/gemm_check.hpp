@@ -289,8 +289,24 @@ inline SinkCheck check_statsink(const float* C, long M, int N, const float* part
 // ---- GradSink ----------------------------------------------------------------------------------
 // part [N][P] (sum dz, sum dz*xhat) of the dgrad's result C through the BN whose input is y [M][N]
 // (gs_one, common.hpp); bounds of the same form over |dz| and |dz*xhat| (+ relu6 kink elements)
+// How far the device's act'(z) may lie from the fp64 one when its z is within ez of z.  swish' =
+// s (1 + z (1 - s)): with E = (|z| + 2)(1 - s) + 3 <= |z| + 5 the relative error of s in units of 2^-24
+// (v_exp of a rounded -z log2 e, the add, v_rcp), the evaluation is off by at most
+// 2^-24 (E + 2)(|g| + s |z|), and |swish''| <= 0.5.  relu6' is piecewise constant (its kinks: near_kink).
+inline double actgrad_err(double z, double ez, int act) {
+  if (act != 1) return 0.0;
+  const double s = 1.0 / (1.0 + std::exp(-z));
+  const double g = s * (1.0 + z * (1.0 - s));
+  return kEps24 * (std::fabs(z) + 7.0) * (std::fabs(g) + s * std::fabs(z)) + 0.5 * ez;
+}
+
+// act_err: add |da| actgrad_err (times |xhat|) per element.  That error is absolute in da, not relative
+// to dz: where swish' is near its zero (z = -1.28) it exceeds any multiple of 2^-24 |dz|.  Over the GEMM
+// cases' thousands of rows the (M + 8) term hides it; the conv checker's 1x1 and 2x2 members (2 and 8
+// rows) need it (conv_parity, conv_teeth pass true; the GEMM checker's bounds are as they were).
 inline SinkCheck check_gradsink(const float* C, long M, int N, const float* y, const float* mu, const float* rstd,
-                                const float* sc, const float* be, int act, const float* part2, int P) {
+                                const float* sc, const float* be, int act, const float* part2, int P,
+                                bool act_err = false) {
   SinkCheck k;
   for (int c = 0; c < N; ++c) {
     double s1 = 0.0, s2 = 0.0;
@@ -317,6 +333,11 @@ inline SinkCheck check_gradsink(const float* C, long M, int N, const float* y, c
       if (near_kink(z, std::fabs(yc * (double)sc[c]) + std::fabs((double)be[c]), act)) {
         j1 += std::fabs(da);
         j2 += std::fabs(da * xh);
+      }
+      if (act_err) {
+        const double eg = actgrad_err(z, kEps24 * (2.0 * std::fabs(yc * (double)sc[c]) + std::fabs(z)), act);
+        j1 += std::fabs(da) * eg;
+        j2 += std::fabs(da * xh) * eg;
       }
     }
     const double b1 = (M + 8) * kEps24 * a1 + j1, b2 = (M + 8) * kEps24 * a2 + j2;
