@@ -273,6 +273,20 @@ int ew_gstats_partials(long seg_rows, int C, int nseg);
 void launch_bn_bwd_finalize(const float2* part, int P, long M, int C, float* mdz, float* mdzx,
                             hipStream_t s);
 size_t colred_scratch_doubles(long seg_rows, int C, int nseg);
+// The column reductions' and the SE MLP's plans (host only, read-only: tests/kernels/norm_parity prints
+// them to hold its case table to the edges).  tpr_last: the lanes per row of the last channel group;
+// depth: the rows a lane of k_colred_part loads before consuming any.
+struct RedPlanInfo {
+  int tpr, rpi, cgroups, chunks, tpr_last, depth;
+  long rpc;
+};
+RedPlanInfo red_plan_info(long seg_rows, int C, int nseg);
+// chunks: the row chunks of the pool reduction (red_plan_info(HW, C, B).chunks); fold_small: k_se_squeeze
+// folds them with kg lane groups per channel (slices of at most 128 channels), else one lane per channel
+struct SePlanInfo {
+  int s1, cs1, s2, cs2, fold_small, kg, jg;
+};
+SePlanInfo se_plan_info(int B, int C, int Cse, int chunks);
 // drop connect (utils.py:329-344) on one operand: v' = (v / p) * keep[image], forward, and
 // (g * keep[image]) / p for its gradient
 struct DropView {

@@ -87,6 +87,19 @@ size_t colred_scratch_doubles(long seg_rows, int C, int nseg) {
 }
 size_t bn_stats_scratch_doubles(long M, int C) { return colred_scratch_doubles(M, C, 1); }
 
+RedPlanInfo red_plan_info(long seg_rows, int C, int nseg) {
+  const RedPlan p = red_plan(seg_rows, C, nseg);
+  RedPlanInfo r;
+  r.tpr = p.tpr;
+  r.rpi = 256 / p.tpr;
+  r.cgroups = p.cgroups;
+  r.chunks = p.chunks;
+  r.rpc = p.rpc;
+  r.tpr_last = C / 4 - (p.cgroups - 1) * 256;  // k_colred_part: tpr = min(tpr_total - g0, 256)
+  r.depth = red_depth();
+  return r;
+}
+
 template <class F, int D>
 __global__ __launch_bounds__(256) void k_colred_part(F f, long seg_rows, int C, long rpc,
                                                      double* __restrict__ part) {
@@ -700,6 +713,7 @@ __global__ __launch_bounds__(256) void k_gx_materialize(GradX g, float4* __restr
 }
 
 void launch_bn_bwd_apply2(GradX g, float* out, long M, int C, hipStream_t s) {
+  if (C % 4) throw std::runtime_error("bn_bwd_apply2: C % 4");
   long n4 = M * C / 4;
   if (g.y && g.ybf)
     hipLaunchKernelGGL(k_gx_materialize<true>, dim3(cdiv(n4, 256)), dim3(256), 0, s, g, (float4*)out, n4, C);
@@ -798,6 +812,18 @@ static SePlan se_plan(int B, int C, int N) {
   p.cs2 = cdiv(C, p.s2);
   p.s2 = cdiv(C, p.cs2);
   return p;
+}
+
+SePlanInfo se_plan_info(int B, int C, int Cse, int chunks) {
+  const SePlan p = se_plan(B, C, Cse);
+  SePlanInfo r;
+  r.s1 = p.s1; r.cs1 = p.cs1; r.s2 = p.s2; r.cs2 = p.cs2;
+  // k_se_squeeze's fold: slices of at most kSeT / 2 channels split the chunks over kg lane groups
+  r.fold_small = p.cs1 <= kSeT / 2 ? 1 : 0;
+  r.kg = r.fold_small ? std::min(chunks, kSeT / p.cs1) : 1;
+  // k_se_excite: jg lane groups over the hidden units
+  r.jg = p.cs2 >= kSeT ? 1 : std::min(8, kSeT / p.cs2);
+  return r;
 }
 
 // BWD = 0: v = mean over HW; BWD = 1: v = (sum dy*x) * s * (1 - s)
@@ -974,6 +1000,7 @@ static void se_mlp(const double* scratch, int chunks, int B, int C, int N, float
 void launch_se_fwd(InX x, float* y, int B, int HW, int C, int Cse, const float* w1,
                    const float* b1, const float* w2, const float* b2, int act, float* pool,
                    float* hidden, float* scale, hipStream_t s, double* scratch) {
+  if (Cse < 1 || Cse > kSeT) throw std::runtime_error("se: squeeze width outside 1..256");
   const int chunks = x.bf ? colred_parts(SumAcc<true>{x, nullptr, C, {}}, HW, C, B, scratch, s)
                           : colred_parts(SumAcc<false>{x, nullptr, C, {}}, HW, C, B, scratch, s);
   se_mlp<0>(scratch, chunks, B, C, Cse, 1.0f / (float)HW, w1, b1, w2, b2, act, nullptr, pool, hidden, scale, s);
@@ -1012,6 +1039,7 @@ int launch_se_bwd(const float* dy, InX x, float* dx, int B, int HW, int C, int C
                   const float* w1, const float* b1, const float* w2t, const float* b2, int act,
                   const float* pool, const float* hidden, const float* scale, float* gsum,
                   bool acc, hipStream_t s, double* scratch, GradSink gs) {
+  if (Cse < 1 || Cse > kSeT) throw std::runtime_error("se: squeeze width outside 1..256");
   (void)b1; (void)b2; (void)pool;
   // gsum[0 .. B*C): dpool
   const int chunks = x.bf ? colred_parts(SumAcc<true>{x, dy, C, {}}, HW, C, B, scratch, s)
@@ -1046,8 +1074,9 @@ __global__ void k_add(InX a, InX b, float* __restrict__ y, long n4, int C, DropV
 }
 
 void launch_add(InX a, InX b, float* y, long n, int C, hipStream_t s, DropView dv) {
-  long n4 = n / 4;
   if (a.bf != b.bf) throw std::runtime_error("add: operands differ in storage type");
+  if (C % 4 || n % C) throw std::runtime_error("add: C % 4 or n % C");
+  long n4 = n / 4;
   if (a.bf) hipLaunchKernelGGL(k_add<true>, dim3(cdiv(n4, 256)), dim3(256), 0, s, a, b, y, n4, C, dv);
   else hipLaunchKernelGGL(k_add<false>, dim3(cdiv(n4, 256)), dim3(256), 0, s, a, b, y, n4, C, dv);
   PHX_LAUNCH_CHECK();
@@ -1162,6 +1191,7 @@ int launch_grad_sums(const float* src, long n, int C, GradSink gs, hipStream_t s
 
 int launch_copy_grad(const float* src, float* dst, long n, bool acc, hipStream_t s, int C,
                      GradSink gs, DropView dv) {
+  if (C % 4 || n % C) throw std::runtime_error("copy_grad: C % 4 or n % C");
   if (gs.part) return ew_gstats(CopyGrad{src, dst, C, acc ? 1 : 0, dv}, n / C, C, 1, gs, s);
   long n4 = n / 4;
   hipLaunchKernelGGL(k_copy_grad, dim3(cdiv(n4, 256)), dim3(256), 0, s, (const float4*)src,
