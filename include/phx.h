@@ -151,6 +151,49 @@ int phx_soft_nms(phx_ctx* ctx, const float* boxes, const float* scores, const in
                  int B, int N, float* out_boxes, float* out_scores, int32_t* out_count,
                  void* stream);
 
+/* ---- serving raw frames ------------------------------------------------------------------
+ * EfficientDetModel.call(raw_frames, training=False, pre_mode='infer', post_mode='global')
+ * (efficientdet_keras.py:912-994), what KerasDriver.serve runs for detector.Detector.infer
+ * (infer_lib.py:408-421, detector.py:35-60), in three entry points.  Frames are a packed batch of
+ * HWC uint8 RGB images of any sizes: src (device) with offsets [B] int64 byte offsets and dims
+ * [B,2] int32 (h, w) — both HOST arrays, so every argument is checked before anything is launched.
+ * PHX_EINVAL with a message naming the argument, nothing launched: B < 1 or B > max_batch, a null
+ * pointer, h or w < 1, a scaled side that truncates to 0 (tf.image.resize raises there), images
+ * not 16-byte aligned.  The first serving call reserves the frame tables (and phx_serve the batch
+ * size's image buffer; both synchronous, counted by phx_workspace_bytes); later calls allocate
+ * nothing and do not synchronise — unless 8 serving calls are still in flight, when the host
+ * waits for the oldest one's frame table.
+ *
+ * _preprocessing(mode='infer') -> DetectionInputProcessor (dataloader.py:59-65, 115-142, 199-201):
+ * (x - mean_rgb) / stddev_rgb in fp32 with the model's own constants; image_scale =
+ * min(fp32(S)/fp32(h), fp32(S)/fp32(w)); tf.image.resize(antialias=True, bilinear) to
+ * [int(h * image_scale), int(w * image_scale)] (truncating fp32 products); top-left placement on a
+ * zero [S,S,3] canvas.  images [B,S,S,3] float32 and scales [B] = image_scale_to_original =
+ * 1 / image_scale (device).  Works in a context of either compute dtype (its output is fp32). */
+int phx_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims,
+                         int B, float* images, float* scales, void* stream);
+/* postprocess_global over caller-provided candidates (postprocess.py:375-406), the class-carrying
+ * sibling of phx_soft_nms: nms(padded=True) on every candidate with score > the context's NMS
+ * threshold (score_thresh, or 0.001 when it is 0) — no person, validity or >= filter —, clip_boxes
+ * to [0, S], then x scales[b] (NULL: boxes stay in model pixels), classes + 1 (CLASS_OFFSET) as
+ * float32.  boxes [B,N,4], scores [B,N], classes [B,N] int32, count [B] valid candidates per row
+ * (NULL: N); out_boxes [B,100,4], out_scores [B,100], out_classes [B,100], out_count [B] (all
+ * device).  Rows at and beyond out_count are zero in every output (TF's padded
+ * NonMaxSuppressionV5 gathers candidate 0 there: read the first out_count rows only). */
+int phx_nms_global(phx_ctx* ctx, const float* boxes, const float* scores, const int32_t* classes,
+                   const int32_t* count, int B, int N, const float* scales, float* out_boxes,
+                   float* out_scores, float* out_classes, int32_t* out_count, void* stream);
+/* The whole call: preprocess, forward, postprocess_global with the frames' image_scale_to_original,
+ * so boxes are in frame pixels.  The forward always runs inference BN from the moving statistics,
+ * without drop connect or moving-statistics update, whatever the context's bn_mode (KerasDriver
+ * forces is_training_bn=False, infer_lib.py:171).  out_scales [B] (NULL = skip) receives
+ * image_scale_to_original.  Needs loaded weights (PHX_ESTATE).  PHX_ESTATE while a phx_set_next
+ * prefetch is in flight (run or withdraw it first).  fp32 contexts only: a PHX_DTYPE_BF16 context is
+ * refused with PHX_EINVAL (phx_serve_preprocess and phx_nms_global work in either). */
+int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
+              float* out_boxes, float* out_scores, float* out_classes, int32_t* out_count,
+              float* out_scales, void* stream);
+
 /* ---- EOT patch pipeline ----------------------------------------------------------------- */
 /* BrightnessMatcher.call((src, tgt)) (brightness_matcher.py:43-73) for one src per image:
  * src [B,P,P,3], tgt [B,H,W,3] -> out [B,P,P,3]. */

@@ -68,6 +68,14 @@ _SIGS = [
     ("phx_first_pass", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_soft_nms", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # serving raw frames (offsets / dims are host arrays)
+    ("phx_serve_preprocess", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("phx_nms_global", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p]),
+    ("phx_serve", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_brightness_match", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("phx_set_matcher", c_int, [c_void_p, c_int]),

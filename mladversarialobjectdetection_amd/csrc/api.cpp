@@ -162,9 +162,18 @@ struct Exec {
   float* inj_boxes = nullptr;
   int* inj_count = nullptr;
   float* dscale_scratch = nullptr;  // dL/dscale of a gradient-free (eval) step
+  // serving (phx_serve): the preprocessed batch [B,S,S,3], image_scale_to_original [B] and the
+  // soft-NMS's selected anchors [B,100]; reserved by the first phx_serve of this batch size
+  float *srv_images = nullptr, *srv_scales = nullptr;
+  int* srv_sel = nullptr;
   double* sync_sums = nullptr;      // bn=sync: [member][C][3] per-channel sums to all-reduce
 
-  int tag = 0;        // 0: the step's executor; 1: the concurrent first pass's (forward only)
+  // planned for inference BN (a bn=frozen context's executors, the serving executor): its forward
+  // chooses each GEMM's kernel by the rows of one image (gemm_plan_images), so an image's result does
+  // not depend on the batch size it was computed in
+  bool infer_plan = false;
+  int tag = 0;        // 0: the step's executor; 1: the concurrent first pass's (forward only);
+                      // 2: phx_serve's in a batch-statistics context (forward only, inference plan)
   // deferred moving statistics (a step whose first pass runs beside the second): while defer_mov
   // the BN finalizes leave the moving statistics alone and write (batch mean, variance) of their
   // slot to side + 2 * side_off[slot]; launch_bn_moving_apply then applies both passes in order
@@ -290,6 +299,20 @@ struct phx_ctx {
   // (chunk counts, lookup tables), grown on demand
   DPtr bm_ws;
   size_t bm_cap = 0;
+  // serving: frame tables of the preprocess (phx_serve_preprocess / phx_serve take host offsets and
+  // dims).  kSrvRing slots of max_batch frames, pinned on the host and mirrored on the device; a
+  // call fills the next slot, copies it on its stream and records the slot's event after its
+  // kernel, so the host waits only when kSrvRing calls are still in flight.  Reserved at the first
+  // serving call; srv_sel_ws: phx_nms_global's selected indices [max_batch,100].
+  static constexpr int kSrvRing = 8;
+  ServeFrame* srv_host = nullptr;
+  DPtr srv_dev;
+  hipEvent_t srv_ev[kSrvRing] = {};
+  bool srv_busy[kSrvRing] = {};
+  int srv_next = 0;
+  DPtr srv_sel_ws;
+  size_t srv_sel_cap = 0;
+  size_t srv_bytes = 0;
   // executor use clock (least-recently-used eviction, see exec_for)
   uint64_t clock = 0;
 
@@ -338,6 +361,9 @@ struct phx_ctx {
     pre = Pre{};
   }
   ~phx_ctx() {
+    for (hipEvent_t e : srv_ev)
+      if (e) (void)hipEventDestroy(e);
+    if (srv_host) (void)hipHostFree(srv_host);
     if (s2) (void)hipStreamSynchronize(s2);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
@@ -545,7 +571,10 @@ bool is_cls_out(const Program& P, int t);
 }  // namespace
 
 // One executor per (batch size, tag) (the program and its arenas are shaped by B; tag 1 is the
-// concurrent first pass's forward-only executor, §12 of DESIGN.md).  At most kMaxExecs stay
+// concurrent first pass's forward-only executor, §12 of DESIGN.md; tag 2 is phx_serve's forward-only
+// executor in a context whose BN mode is not frozen, planned for inference BN exactly as a
+// bn=frozen context's tag 0, so that serving computes the same bits whatever the context's mode).
+// At most kMaxExecs stay
 // alive, two per batch size for two batch sizes, so a driver that mixes batch sizes (a last
 // partial batch, validation) keeps both sizes' step and side executors without evicting at every
 // switch.  A third batch size evicts (after the device has drained, so no queued kernel still
@@ -579,13 +608,16 @@ Exec& phx_ctx::exec_for(int B, int tag) {
   E.tag = tag;
   E.bf16 = bf16;
   E.abf = bf16;
-  NetBuilder nb(mc, B, batch_bn());
+  // the serving executor (tag 2) is planned as a bn=frozen context plans: inference BN only
+  const bool bbn = tag == 2 ? false : batch_bn();
+  E.infer_plan = !bbn;
+  NetBuilder nb(mc, B, bbn);
   nb.build();
   E.prog = nb.program();
   Program& P = E.prog;
   E.act = E.alloc<float>(E.abf ? (P.act_floats + 1) / 2 : P.act_floats);
   // the concurrent first pass's executor (tag 1) runs forwards only: no gradient arena
-  E.grad = E.alloc<float>(tag == 1 ? 1 : P.grad_floats);
+  E.grad = E.alloc<float>(tag != 0 ? 1 : P.grad_floats);
   // statistics slots and scratch
   E.slot_a.assign(P.n_slots, nullptr);
   E.slot_b.assign(P.n_slots, nullptr);
@@ -642,7 +674,7 @@ Exec& phx_ctx::exec_for(int B, int tag) {
   E.fused_bn.assign(P.ops.size(), 0);
   E.stat_P.assign(P.tensors.size(), 0);
   size_t sp_need = 1, sc_need = 1;
-  if (batch_bn()) {
+  if (bbn) {
     for (size_t i = 1; i < P.ops.size(); ++i) {
       const Op& op = P.ops[i];
       const Op& pr = P.ops[i - 1];
@@ -661,7 +693,7 @@ Exec& phx_ctx::exec_for(int B, int tag) {
   }
   E.gfused_bn.assign(P.ops.size(), 0);
   E.gstat_P.assign(P.ops.size(), 0);
-  if (batch_bn()) {
+  if (bbn) {
     for (size_t i = 0; i + 1 < P.ops.size(); ++i) {
       const Op& bn = P.ops[i];
       const Op& L = P.ops[i + 1];
@@ -684,8 +716,8 @@ Exec& phx_ctx::exec_for(int B, int tag) {
       sp_need = std::max(sp_need, (size_t)np * tz.c);
     }
   }
-  plan_groups(E, batch_bn());
-  if (bn_mode == PHX_BN_SYNC) {
+  plan_groups(E, bbn);
+  if (bn_mode == PHX_BN_SYNC && tag != 2) {
     int cmax = 1;
     for (const Tensor& t : P.tensors) cmax = std::max(cmax, t.c);
     E.sync_sums = E.alloc<double>((size_t)kMaxSeg * cmax * 3);
@@ -768,7 +800,7 @@ Exec& phx_ctx::exec_for(int B, int tag) {
   E.sepb.assign(P.ops.size(), 0);
   {
     const char* sb = std::getenv("PHX_SEPB");
-    const bool on = !(sb && sb[0] == '0') && batch_bn();
+    const bool on = !(sb && sb[0] == '0') && bbn;
     for (size_t i = 0; on && i + 1 < P.ops.size(); ++i) {
       if (!E.sep[i]) continue;
       const int gd = E.grp_of[i];
@@ -887,8 +919,8 @@ Exec& phx_ctx::exec_for(int B, int tag) {
   E.ymean = E.alloc<float>((size_t)B * 2);
   // the resized patches; reused by the resize adjoint's row buffer once the rotation backward
   // has consumed them
-  // (the concurrent first pass's executor runs no EOT: its patch stores stay one element)
-  const bool eot = tag != 1;
+  // (the concurrent first pass's and the serving executor run no EOT: their patch stores stay one element)
+  const bool eot = tag == 0;
   E.rstore = E.alloc<float>(eot ? std::max(E.ed.rcap, eot_resize_scratch_floats(E.ed)) : 1);
   E.dstore = E.alloc<float>(eot ? E.ed.rcap : 1);
   const size_t np = (size_t)PHX_PATCH_SIZE * PHX_PATCH_SIZE * 3;
@@ -1461,6 +1493,11 @@ void run_forward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s, int p
                  int gimg0, bool train = true, bool force_frozen = false) {
   const Program& P = E.prog;
   float* W = ctx->w();
+  struct PlanImages {
+    int& n = gemm_plan_images();
+    explicit PlanImages(int v) { n = v; }
+    ~PlanImages() { n = 0; }
+  } plan_images(E.infer_plan ? E.B : 0);
   const bool frozen = ctx->bn_mode == PHX_BN_FROZEN || !train || force_frozen;
   // inference BN: the statistics from the moving averages are a function of the weights, so the
   // slots keep them from the last inference pass at the same weights version (the frozen protege of
@@ -1898,7 +1935,8 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
 
 // cand_mask: the keep bits whose anchors (above the NMS threshold) pre_nms appends to the
 // soft-NMS candidate list (2: the first pass's person/valid/>=thresh, 1: the second pass's
-// person/valid for the ASR metric, 0: no list); the run_nms that follows consumes it
+// person/valid for the ASR metric, 4: person, -1: every anchor (serving, postprocess_global), 0: no
+// list); the run_nms that follows consumes it
 // nms_t: the soft-NMS score threshold of the candidate list (< 0: the context's)
 void run_pre_nms(phx_ctx* ctx, Exec& E, hipStream_t s, int cand_mask = 0, float nms_t = -1.f) {
   const Program& P = E.prog;
@@ -1919,12 +1957,12 @@ void run_pre_nms(phx_ctx* ctx, Exec& E, hipStream_t s, int cand_mask = 0, float 
 
 // postprocess.nms with method 'gaussian': sigma 0.5 -> soft_nms_sigma 0.25
 void run_nms(phx_ctx* ctx, Exec& E, int keep_mask, float* ob, float* os, int* oc, hipStream_t s,
-             float nms_t = -1.f) {
+             float nms_t = -1.f, int* sel = nullptr) {
   Scope scope(ctx, "soft_nms", 0.0, (double)E.B * ctx->A * 5.0, s);
   const float t = nms_t < 0.f ? ctx->nms_thresh : nms_t;
   launch_soft_nms(E.boxes, E.scores, E.keep, keep_mask, nullptr, E.B, ctx->A, t,
                   0.25f, PHX_MAX_OUT, (float)ctx->mc.image_size, ob, os, oc, E.nms_ws, s,
-                  NmsCand{E.cand_list, E.cand_count, keep_mask, t});
+                  NmsCand{E.cand_list, E.cand_count, keep_mask, t}, sel);
 }
 
 // PHX_GUARD_BYTES: after a step, every executor allocation's guard band must still be 0xA5
@@ -2152,7 +2190,7 @@ int phx_workspace_bytes(phx_ctx* ctx, int B, size_t* bytes) {
   size_t tot = ctx->exec_for(B).bytes;
   for (const auto& e : ctx->execs)  // + the concurrent first pass's executor, once a step made it
     if (e->B == B && e->tag != 0) tot += e->bytes;
-  *bytes = tot;
+  *bytes = tot + ctx->srv_bytes;  // + the serving frame tables, once a serving call made them
   return PHX_OK;
   PHX_CATCH(ctx)
 }
@@ -2246,6 +2284,171 @@ int phx_soft_nms(phx_ctx* ctx, const float* boxes, const float* scores, const in
   }
   launch_soft_nms(boxes, scores, nullptr, 0, count, B, N, ctx->nms_thresh, 0.25f, PHX_MAX_OUT,
                   (float)ctx->mc.image_size, ob, os, oc, (float*)ctx->sn_ws.get(), s);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+namespace {
+
+// The frame table of a serving call, sized as DetectionInputProcessor does in fp32
+// (dataloader.py:115-127: image_scale = min(S / h, S / w), scaled = int(side * image_scale)), and
+// every argument check of phx_serve_preprocess / phx_serve.  Host arithmetic only: a refused call
+// has launched nothing.  Returns the message of the first bad argument ("" = fine).
+std::string serve_frames(const phx_ctx* ctx, const char* fn, const void* src, const int64_t* offsets,
+                         const int32_t* dims, int B, std::vector<ServeFrame>* out) {
+  const std::string who = std::string(fn) + ": ";
+  if (B < 1 || B > ctx->max_batch)
+    return who + "B = " + std::to_string(B) + " outside [1, max_batch = " + std::to_string(ctx->max_batch) + "]";
+  if (!src) return who + "src is null";
+  if (!offsets) return who + "offsets is null";
+  if (!dims) return who + "dims is null";
+  const int S = ctx->mc.image_size;
+  if (S % 4) return who + "image_size " + std::to_string(S) + " is not a multiple of 4";
+  out->resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int h = dims[2 * b], w = dims[2 * b + 1];
+    const std::string at = who + "dims[" + std::to_string(b) + "] = " + std::to_string(h) + "x" + std::to_string(w);
+    if (h < 1 || w < 1) return at + ": h and w must be >= 1";
+    if (offsets[b] < 0) return who + "offsets[" + std::to_string(b) + "] is negative";
+    const float sy = (float)S / (float)h, sx = (float)S / (float)w;
+    const float sc = std::fmin(sy, sx);
+    const int sh = (int)((float)h * sc), sw = (int)((float)w * sc);  // truncating fp32 products
+    // tf.image.resize raises on an empty size
+    if (sh < 1) return at + ": scaled height int(h * image_scale) is 0 at image_size " + std::to_string(S);
+    if (sw < 1) return at + ": scaled width int(w * image_scale) is 0 at image_size " + std::to_string(S);
+    if (sh > S || sw > S) return at + ": scaled size exceeds image_size";
+    const float inv = 1.0f / sc;
+    (*out)[b] = ServeFrame{offsets[b], h, w, sh, sw, inv, 0};
+  }
+  return "";
+}
+
+// the next slot of the frame-table ring, filled and copied on `s`; the caller records srv_ev[slot]
+// on `s` after the kernel that reads the table
+const ServeFrame* serve_stage(phx_ctx* ctx, const std::vector<ServeFrame>& fr, hipStream_t s, int* slot_out) {
+  const size_t slot_frames = (size_t)ctx->max_batch;
+  if (!ctx->srv_host) {
+    const size_t n = slot_frames * phx_ctx::kSrvRing;
+    void* hp = nullptr;
+    PHX_HIP(hipHostMalloc(&hp, n * sizeof(ServeFrame), hipHostMallocDefault));
+    ctx->srv_host = static_cast<ServeFrame*>(hp);
+    ctx->srv_dev.reset(dalloc<ServeFrame>(n));
+    for (hipEvent_t& e : ctx->srv_ev) PHX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ctx->srv_bytes += n * sizeof(ServeFrame);
+  }
+  const int slot = ctx->srv_next;
+  ctx->srv_next = (slot + 1) % phx_ctx::kSrvRing;
+  if (ctx->srv_busy[slot]) PHX_HIP(hipEventSynchronize(ctx->srv_ev[slot]));  // kSrvRing calls in flight
+  ctx->srv_busy[slot] = false;
+  ServeFrame* h = ctx->srv_host + slot * slot_frames;
+  ServeFrame* d = static_cast<ServeFrame*>(ctx->srv_dev.get()) + slot * slot_frames;
+  std::memcpy(h, fr.data(), fr.size() * sizeof(ServeFrame));
+  PHX_HIP(hipMemcpyAsync(d, h, fr.size() * sizeof(ServeFrame), hipMemcpyHostToDevice, s));
+  *slot_out = slot;
+  return d;
+}
+
+void serve_preprocess(phx_ctx* ctx, const uint8_t* src, const std::vector<ServeFrame>& fr, float* images,
+                      float* scales, hipStream_t s) {
+  const int B = (int)fr.size(), S = ctx->mc.image_size;
+  double bytes = 0;
+  for (const ServeFrame& f : fr) bytes += (double)f.h * f.w * 3 + 12.0 * S * S;
+  Scope scope(ctx, "preprocess", 0.0, bytes, s);
+  int slot = 0;
+  const ServeFrame* d = serve_stage(ctx, fr, s, &slot);
+  launch_serve_preprocess(src, d, B, S, ctx->mc.mean_rgb, ctx->mc.stddev_rgb, images, scales, s);
+  PHX_HIP(hipEventRecord(ctx->srv_ev[slot], s));
+  ctx->srv_busy[slot] = true;
+}
+
+}  // namespace
+
+int phx_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
+                         float* images, float* scales, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  std::vector<ServeFrame> fr;
+  const std::string bad = serve_frames(ctx, "serve_preprocess", src, offsets, dims, B, &fr);
+  if (!bad.empty()) return fail(ctx, PHX_EINVAL, bad);
+  if (!images) return fail(ctx, PHX_EINVAL, "serve_preprocess: images is null");
+  if (!scales) return fail(ctx, PHX_EINVAL, "serve_preprocess: scales is null");
+  if (reinterpret_cast<uintptr_t>(images) & 15)
+    return fail(ctx, PHX_EINVAL, "serve_preprocess: images is not 16-byte aligned");
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  serve_preprocess(ctx, src, fr, images, scales, (hipStream_t)stream);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_nms_global(phx_ctx* ctx, const float* boxes, const float* scores, const int32_t* classes,
+                   const int32_t* count, int B, int N, const float* scales, float* ob, float* os, float* ocl,
+                   int32_t* oc, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  if (B < 1 || N < 1) return fail(ctx, PHX_EINVAL, "nms_global: B and N must be >= 1");
+  if (!boxes || !scores || !classes || !ob || !os || !ocl || !oc)
+    return fail(ctx, PHX_EINVAL, "nms_global: null boxes, scores, classes or output pointer");
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t need = soft_nms_work_floats(B, N);
+  if (need > ctx->sn_cap) {
+    PHX_HIP(hipStreamSynchronize(s));
+    ctx->sn_ws.reset(dalloc<float>(need));
+    ctx->sn_cap = need;
+  }
+  const size_t nsel = (size_t)B * PHX_MAX_OUT;
+  if (nsel > ctx->srv_sel_cap) {
+    PHX_HIP(hipStreamSynchronize(s));
+    ctx->srv_sel_ws.reset(dalloc<int>(nsel));
+    ctx->srv_sel_cap = nsel;
+  }
+  int* sel = static_cast<int*>(ctx->srv_sel_ws.get());
+  // nms(padded=True) on every candidate above the threshold, boxes clipped to [0, S] by the kernel
+  launch_soft_nms(boxes, scores, nullptr, 0, count, B, N, ctx->nms_thresh, 0.25f, PHX_MAX_OUT,
+                  (float)ctx->mc.image_size, ob, os, oc, (float*)ctx->sn_ws.get(), s, NmsCand{}, sel);
+  launch_nms_global_epilogue(sel, oc, classes, scales, B, N, PHX_MAX_OUT, ob, ocl, s);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B, float* ob,
+              float* os, float* ocl, int32_t* oc, float* out_scales, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  std::vector<ServeFrame> fr;
+  const std::string bad = serve_frames(ctx, "serve", src, offsets, dims, B, &fr);
+  if (!bad.empty()) return fail(ctx, PHX_EINVAL, bad);
+  if (!ob || !os || !ocl || !oc)
+    return fail(ctx, PHX_EINVAL, "serve: null out_boxes, out_scores, out_classes or out_count");
+  if (ctx->bf16)
+    return fail(ctx, PHX_EINVAL, "serve: a PHX_DTYPE_BF16 context does not serve (fp32 contexts only)");
+  PHX_TRY(ctx)
+  check_ready(ctx, B);
+  // a prefetched first pass (phx_set_next) holds the side executor and its deferred statistics; an
+  // executor built here could evict it, and a training pass in flight on the side stream moves the
+  // moving statistics this forward reads
+  if (ctx->pre.pending)
+    throw std::logic_error("serve: a phx_set_next prefetch is pending (run or withdraw it first)");
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  // a bn=frozen context's own executor is already planned for inference BN; the others serve from
+  // one planned the same way (tag 2), so the result does not depend on bn_mode
+  Exec& E = ctx->exec_for(B, ctx->batch_bn() ? 2 : 0);
+  const int S = ctx->mc.image_size;
+  if (!E.srv_images) {  // the first serving call of this batch size reserves its buffers
+    E.srv_images = E.alloc<float>((size_t)B * S * S * 3);
+    E.srv_scales = E.alloc<float>(B);
+    E.srv_sel = E.alloc<int>((size_t)B * PHX_MAX_OUT);
+  }
+  serve_preprocess(ctx, src, fr, E.srv_images, E.srv_scales, s);
+  // KerasDriver builds the model with is_training_bn=False (infer_lib.py:171) and calls it with
+  // training=False: inference BN, no drop connect, moving statistics untouched
+  run_forward(ctx, E, E.srv_images, s, 2, 0, 0, false);
+  // postprocess_global (postprocess.py:375-406): pre_nms over all classes, nms(padded=True) on every
+  // anchor above the threshold, clip to [0, S], x image_scale_to_original, classes + CLASS_OFFSET
+  run_pre_nms(ctx, E, s, -1);
+  run_nms(ctx, E, -1, ob, os, oc, s, -1.f, E.srv_sel);
+  launch_nms_global_epilogue(E.srv_sel, oc, E.classes, E.srv_scales, B, ctx->A, PHX_MAX_OUT, ob, ocl, s);
+  if (out_scales) PHX_HIP(hipMemcpyAsync(out_scales, E.srv_scales, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
   return PHX_OK;
   PHX_CATCH(ctx)
 }

@@ -71,6 +71,14 @@ struct Gemm2Plan {
 };
 Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16 = false, bool allow_res = true,
                      bool allow_wsk = true);
+// Batch-invariant inference plans.  While this is n >= 1 (set by the forward of an executor planned
+// for inference BN: its batch size), the choices that change the order of a sum are made for one
+// image, so an image's result does not depend on how many images share the launch: plan_gemm2's
+// wave-split-K kernel (k_gemm2k: K split over a workgroup's waves) against k_gemm2 (K in order) is
+// chosen for M / n rows where K >= 256 and never for the few-tile K < 256 shapes (k_gemm2's order, which
+// the fused separable conv keeps too), and the column reductions (the SE pools) chunk their rows
+// for a fixed number of images.  Tiles, grids and workspaces still follow the launch.  0 (default): off.
+int& gemm_plan_images();
 void gemm2_force_cfg(int wm, int tm, int tn, int splits);  // tools/gemm_bench sweeps only (0 = off)
 void gemm2_force_wsk(int tm, int tn);                       // tools/gemm_bench sweeps only (0 = off, -1 = never)
 struct Gemm2Args;
@@ -355,10 +363,12 @@ void launch_pre_nms(const float* cls_base, const float* box_base, const LevelDes
                     float* boxes, uint8_t* keep, int ntiles, hipStream_t s, NmsCand cand = NmsCand{},
                     bool bf = false);  // bf: class / box outputs in bf16 storage
 // soft-NMS (NonMaxSuppressionV5, gaussian) per image over candidates selected by keep&mask
+// out_index (nullable) [B,max_out]: each selection's index into boxes / scores (-1 beyond the count)
 void launch_soft_nms(const float* boxes, const float* scores, const uint8_t* keep, int keep_mask,
                      const int* count, int B, int N, float score_thresh, float soft_sigma,
                      int max_out, float clip_hi, float* out_boxes, float* out_scores,
-                     int* out_count, float* work, hipStream_t s, NmsCand cand = NmsCand{});
+                     int* out_count, float* work, hipStream_t s, NmsCand cand = NmsCand{},
+                     int* out_index = nullptr);
 // work floats of launch_soft_nms (compacted candidate boxes, spilled queue keys, anchors, visits)
 size_t soft_nms_work_floats(int B, int N);
 // per-image m_b = max(max_{keep} score, 0), tie count, and loss-gradient coefficient
@@ -371,6 +381,22 @@ size_t image_max_scratch_ints(int B);
 // -> out [B,oh,ow,3] normalised, cv2-INTER_LINEAR-resized, top-left letterboxed, zero padded
 void launch_letterbox(const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
                       const float* mean, const float* stdv, int oh, int ow, float* out, hipStream_t s);
+// ---- serving path (kernels_serve.hip, dataloader.py:59-201 + postprocess.py:375-406) ---------
+// one frame of a packed uint8 batch, sized on the host (dataloader.py:115-127 in fp32)
+struct ServeFrame {
+  int64_t offset;           // byte offset of the frame in src
+  int h, w;                 // frame size
+  int sh, sw;               // int(h * image_scale), int(w * image_scale)
+  float scale_to_original;  // 1 / image_scale
+  int pad_;
+};
+// normalise + antialiased resize + zero pad of B frames -> images [B,S,S,3], scales [B]; S % 4 == 0
+void launch_serve_preprocess(const uint8_t* src, const ServeFrame* frames_dev, int B, int S, const float* mean,
+                             const float* stdv, float* images, float* scales, hipStream_t s);
+// after launch_soft_nms with a selected-index output: out_classes [B,max_out] = classes[sel] + 1 as
+// float, boxes *= scales[b] (scales may be null); rows >= count[b] get class 0
+void launch_nms_global_epilogue(const int* sel, const int* count, const int* classes, const float* scales, int B,
+                                int N, int max_out, float* boxes, float* out_classes, hipStream_t s);
 // flip -> RandomFlip -> RandomContrast(.2) -> random_brightness(.2) -> clip; in/out [B,H,W,3]
 size_t augment_scratch_doubles(int B);
 void launch_augment(const float* in, float* out, int B, int H, int W, uint64_t seed, int64_t step,

@@ -91,9 +91,18 @@ static int wsk_pick(int M, int N) {
   return best;
 }
 
+int& gemm_plan_images() {
+  static thread_local int n = 0;
+  return n;
+}
+
 Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_res, bool allow_wsk) {
   Gemm2Plan p;
   G2Cfg c = g2_pick(N, K, bf16);
+  // the rows the kernel choice below is made for (gemm_plan_images)
+  const int img = gemm_plan_images();
+  const int Mi = img >= 1 && M % img == 0 ? M / img : M;
+  G2Cfg ci = c;
   if (g_force[0]) {
     p.wm = g_force[0]; p.tm = g_force[1]; p.tn = g_force[2];
     c = G2Cfg{p.wm, p.tm, p.tn};
@@ -122,12 +131,19 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
       const char* e = std::getenv("PHX_TILES_FIRST");
       return e && e[0] == '1';
     }();
-    const bool splits = !tiles_first && wgs(c) < 256 && K >= 256;  // split-K covers these
-    if (!splits) {
-      if (c.wm == 4 && c.tm == 1 && c.tn == 2 && wgs(c) < 512) c = G2Cfg{2, 1, 1};
-      if (c.wm == 2 && c.tm == 2 && c.tn == 2 && wgs(c) < 512) c = G2Cfg{2, 1, 2};
-      if (c.wm == 2 && c.tm == 1 && c.tn == 2 && wgs(c) < 512) c = G2Cfg{1, 1, 1};
-    }
+    auto halve = [&](G2Cfg q, int Mx) {
+      auto wgx = [&](const G2Cfg& r) { return (long)cdiv(Mx, r.bm()) * cdiv(N, r.bn()); };
+      const bool splits = !tiles_first && wgx(q) < 256 && K >= 256;  // split-K covers these
+      if (!splits) {
+        if (q.wm == 4 && q.tm == 1 && q.tn == 2 && wgx(q) < 512) q = G2Cfg{2, 1, 1};
+        if (q.wm == 2 && q.tm == 2 && q.tn == 2 && wgx(q) < 512) q = G2Cfg{2, 1, 2};
+        if (q.wm == 2 && q.tm == 1 && q.tn == 2 && wgx(q) < 512) q = G2Cfg{1, 1, 1};
+      }
+      return q;
+    };
+    (void)wgs;
+    ci = halve(c, Mi);
+    c = halve(c, M);
   }
   p.wm = c.wm; p.tm = c.tm; p.tn = c.tn;
   p.mtiles = cdiv(M, c.bm());
@@ -175,9 +191,20 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
     const char* e = std::getenv("PHX_GEMM_WSK_SMALL");
     return !(e && e[0] == '0');
   }();
-  const bool few = wsk_small && p.splits == 1 && (long)p.mtiles * p.gy < 128;
+  // splits / few as this function finds them for Mi rows (= p.splits and the tile count when Mi == M)
+  const long tiles_i = (long)cdiv(Mi, ci.bm()) * cdiv(N, ci.bn());
+  int splits_i = 1;
+  if (tiles_i < split_below && K >= 256)
+    splits_i = std::max(1, std::min<int>((int)((2 * split_below + tiles_i - 1) / tiles_i), K / 128));
+  {
+    const int ks = ((K + splits_i - 1) / splits_i + bk - 1) / bk * bk;
+    splits_i = (K + ks - 1) / ks;
+  }
+  // (not in a batch-invariant forward: whether a K < 256 conv has few tiles follows the launch, and
+  // the fused separable conv, chosen by the launch's rows, keeps k_gemm2's K order)
+  const bool few = wsk_small && img < 1 && splits_i == 1 && tiles_i < 128;
   if (allow_res && allow_wsk && g_force_wsk[0] >= 0 &&
-      (wsk_forced || (wsk_on && (p.splits > 1 || few) && (!bf16 || (wsk_bf16 && !bf16_keep))))) {
+      (wsk_forced || (wsk_on && (splits_i > 1 || few) && (!bf16 || (wsk_bf16 && !bf16_keep))))) {
     p.wsk = wsk_forced ? g_force_wsk[0] * 10 + g_force_wsk[1] : wsk_pick(M, N);
     p.tm = p.wsk / 10;
     p.tn = p.wsk % 10;

@@ -63,7 +63,11 @@ static long red_min_rows(int nseg) {
   return nseg > 1 ? v : v1;
 }
 
-static RedPlan red_plan(long seg_rows, int C, int nseg) {
+// segments the chunking is planned for under gemm_plan_images() (a batch-invariant inference
+// forward: its only column reductions are the SE pools, one segment per image)
+constexpr int kRedPlanImages = 16;
+
+static RedPlan red_plan_for(long seg_rows, int C, int nseg) {
   RedPlan p;
   int tpr_total = C / 4;
   p.cgroups = (tpr_total + 255) / 256;
@@ -81,9 +85,16 @@ static RedPlan red_plan(long seg_rows, int C, int nseg) {
   return p;
 }
 
+// the rows of a chunk decide the order of a segment's sum: planned for the launch's segments, or, in
+// a batch-invariant forward, for a fixed number of them whatever the batch size
+static RedPlan red_plan(long seg_rows, int C, int nseg) {
+  return red_plan_for(seg_rows, C, gemm_plan_images() >= 1 ? kRedPlanImages : nseg);
+}
+
+// (room for either chunking)
 size_t colred_scratch_doubles(long seg_rows, int C, int nseg) {
-  RedPlan p = red_plan(seg_rows, C, nseg);
-  return (size_t)nseg * p.chunks * C * 2 + (size_t)nseg * C * 2;
+  const int chunks = std::max(red_plan_for(seg_rows, C, nseg).chunks, red_plan_for(seg_rows, C, kRedPlanImages).chunks);
+  return (size_t)nseg * chunks * C * 2 + (size_t)nseg * C * 2;
 }
 size_t bn_stats_scratch_doubles(long M, int C) { return colred_scratch_doubles(M, C, 1); }
 

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_pre_nms(const float* __restrict__ cls_b
   }
   if (am == 0) kf |= 4;  // person, before the validity filter (the defender's odet_model)
   keep[idx] = kf;
-  want = (kf & cand.mask) != 0 && sc > cand.thresh;
+  want = (cand.mask < 0 || (kf & cand.mask) != 0) && sc > cand.thresh;
   }
   if (cand.list) nms_cand_append(cand, b, A, want, a);
 }
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
     float score_thresh, float scale, int max_out, float clip_hi, float* __restrict__ out_boxes,
     float* __restrict__ out_scores, int* __restrict__ out_count, float4* __restrict__ cbox_all,
     uint32_t* __restrict__ gkey_all, int* __restrict__ gwi_all, uint8_t* __restrict__ gwb_all,
-    NmsCand cand, NmsPlan pl, int dbg) {
+    NmsCand cand, NmsPlan pl, int dbg, int* __restrict__ out_index) {
   extern __shared__ __attribute__((aligned(16))) unsigned char nms_smem[];
   const int b = blockIdx.x;
   // wave: readfirstlane makes it (and everything decided in wave 0's queue loop) uniform to the
@@ -719,9 +719,10 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
         };
         // a new selection: lane 0 records it; the row's candidates not popped yet (lanes >= j0) take
         // its decay factor into their product
-        auto select = [&](float4 b4, float sc, int j0) {
+        auto select = [&](float4 b4, float sc, int j0, int pos) {
           const NmsNBox sn = nms_norm(b4);
           if (lane == 0) {
+            if (out_index) out_index[(long)b * max_out + nsel] = gwi[pos];
             s_sel[nsel] = b4;
             s_sels[nsel] = sc;
             s_seln[nsel] = make_float4(sn.y0, sn.x0, sn.y1, sn.x1);
@@ -805,7 +806,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
             }
             const float sc = nms_visit_n(nms_norm(b4), orig, from, nsel, s_seln, s_sela, scale, lane);
             uint64_t nk = 0ull;
-            if (sc == orig) select(b4, sc, jn);
+            if (sc == orig) select(b4, sc, jn, pos);
             else if (sc > score_thresh) nk = nms_key(__float_as_uint(sc), pos);
             if (cur) {
               if (lane == owner) {
@@ -833,7 +834,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
               ++ndirty;
             } else sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), j));
             if (sc == orig) {
-              select(readlane_f4(cbx, j), sc, jn);
+              select(readlane_f4(cbx, j), sc, jn, pos);
             } else if (sc > score_thresh) {
               const uint64_t nk = nms_key(__float_as_uint(sc), pos);
               if (lane == j) {
@@ -949,6 +950,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
         if (lane == 0) {
           s_sel[nsel] = cb4;
           s_sels[nsel] = sc;
+          if (out_index) out_index[(long)b * max_out + nsel] = gwi[c];
         }
         ++nsel;
         nk = 0u;
@@ -1004,6 +1006,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
     } else {
       ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
       out_scores[(long)b * max_out + k] = 0.f;
+      if (out_index) out_index[(long)b * max_out + k] = -1;
     }
   }
   if (t == 0) out_count[b] = nsel;
@@ -1023,7 +1026,7 @@ static int nms_debug() {
 void launch_soft_nms(const float* boxes, const float* scores, const uint8_t* keep, int keep_mask,
                      const int* count, int B, int N, float score_thresh, float soft_sigma,
                      int max_out, float clip_hi, float* out_boxes, float* out_scores,
-                     int* out_count, float* work, hipStream_t s, NmsCand cand) {
+                     int* out_count, float* work, hipStream_t s, NmsCand cand, int* out_index) {
   if (max_out > PHX_MAX_OUT_DEV || max_out > 128) throw std::runtime_error("soft_nms: max_out too large");
   const NmsPlan pl = nms_plan(N);
   if (pl.lds > kNmsLdsBytes || pl.nchunk > 64 * kNmsGroups) throw std::runtime_error("soft_nms: too many candidates");
@@ -1043,7 +1046,7 @@ void launch_soft_nms(const float* boxes, const float* scores, const uint8_t* kee
   (void)attr;
   hipLaunchKernelGGL(k_soft_nms, dim3(B), dim3(kNmsThreads), pl.lds, s, boxes, scores, keep, keep_mask,
                      count, N, score_thresh, scale, max_out, clip_hi, out_boxes, out_scores, out_count,
-                     cbox, gkey, gwi, gwb, cand, pl, nms_debug());
+                     cbox, gkey, gwi, gwb, cand, pl, nms_debug(), out_index);
   PHX_LAUNCH_CHECK();
 }
 

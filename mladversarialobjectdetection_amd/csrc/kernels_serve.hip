@@ -1,0 +1,212 @@
+// kernels_serve.hip — the serving path around the detector forward (Detector.infer):
+//   preprocess   EfficientDetModel._preprocessing(mode='infer') -> DetectionInputProcessor
+//                (automl/efficientdet/dataloader.py:59-65 normalize_image, :115-127
+//                set_scale_factors_to_output_size, :129-142 resize_and_crop_image with
+//                tf.image.resize(antialias=True) + pad_to_bounding_box, :199-201 image_scale_to_original)
+//   epilogue     postprocess_global's class gather and rescale (postprocess.py:375-406) after the
+//                soft-NMS kernel, which has clipped the boxes to [0, S] (clip_boxes, :61-64)
+//
+// k_serve_pre: one launch for a packed batch of uint8 frames of any sizes, no intermediate tensor in
+// HBM.  A workgroup owns kServeRows canvas rows x 1024 consecutive canvas floats (256 lanes x one
+// 16-B store per row).  It walks the source rows its canvas rows' vertical spans cover; each source
+// row's bytes under the workgroup's horizontal spans are staged into LDS as normalised floats (one
+// table lookup per byte, dword loads where the dword lies inside the frame), in chunks of
+// kServeChunk pixels, and every lane runs the horizontal taps of its four canvas elements from LDS
+// (the resized source row: a row buffer of one element per lane, kept in registers since the lane
+// that produces an element is the one that consumes it), then adds the row into its canvas rows
+// with the vertical weights.  Spans and weights are TF's ScaleAndTranslate (span.hpp), each axis
+// with its own scaled/in ratio; tap counts are unbounded (loops, no tap arrays).  Canvas elements
+// outside [scaled_h, scaled_w] are stored as 0: the kernel pads, there is no memset.
+// Algorithmic bytes per frame: h*w*3 read + 12*S*S written.
+#include <stdexcept>
+
+#include "common.hpp"
+#include "kernels.hpp"
+
+#pragma clang fp contract(off)
+
+#include "span.hpp"
+
+namespace phx {
+
+constexpr int kServeRows = 4;      // canvas rows per workgroup
+constexpr int kServeChunk = 1024;  // source pixels staged per pass (12 KB of floats)
+
+struct ServePreArgs {
+  const uint8_t* src;
+  const ServeFrame* frames;
+  float mean[3], std[3];
+  int S;
+  float* images;
+  float* scales;
+};
+
+__global__ __launch_bounds__(256) void k_serve_pre(ServePreArgs a) {
+  __shared__ float tab[3 * 256];                               // (byte - mean[c]) / std[c]
+  __shared__ __attribute__((aligned(16))) float row[kServeChunk * 3 + 8];  // a staged chunk, dword-aligned
+  const int t = threadIdx.x;
+  const int b = blockIdx.z;
+  const ServeFrame f = a.frames[b];
+  const int S = a.S, h = f.h, w = f.w, sh = f.sh, sw = f.sw;
+  const int i0 = blockIdx.y * kServeRows;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) a.scales[b] = f.scale_to_original;
+  for (int k = t; k < 3 * 256; k += 256) {
+    const int c = k >> 8;
+    tab[k] = ((float)(k & 255) - a.mean[c]) / a.std[c];
+  }
+  // this lane's four canvas elements of each row: floats e0 .. e0 + 3 of the row's S * 3
+  const int e0 = (blockIdx.x * 256 + t) * 4;
+  const bool lane_on = e0 < S * 3;
+  SpanEntry spx[4];
+  int cx[4];
+  bool onx[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int px = (e0 + j) / 3;
+    cx[j] = (e0 + j) - px * 3;
+    onx[j] = lane_on && px < sw;
+    spx[j] = SpanEntry{0, 0, 0.f, 0.f};
+    if (onx[j]) tf_span(px, sw, w, &spx[j]);
+  }
+  // the workgroup's canvas pixels [p_lo, p_hi] inside the resized image and their source columns
+  const int p_lo = blockIdx.x * 1024 / 3;
+  const int p_hi = min(sw - 1, (blockIdx.x * 1024 + 1023) / 3);
+  // its canvas rows inside the resized image and their source rows
+  const int nrow = min(kServeRows, sh - i0);  // <= 0: padding rows only
+  SpanEntry spy[kServeRows];
+#pragma unroll
+  for (int r = 0; r < kServeRows; ++r) {
+    spy[r] = SpanEntry{0, 0, 0.f, 0.f};
+    if (r < nrow) tf_span(i0 + r, sh, h, &spy[r]);
+  }
+  float acc[kServeRows][4];
+#pragma unroll
+  for (int r = 0; r < kServeRows; ++r)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[r][j] = 0.f;
+  __syncthreads();  // tab
+  if (nrow > 0 && p_lo <= p_hi) {
+    SpanEntry s0, s1;
+    tf_span(p_lo, sw, w, &s0);
+    tf_span(p_hi, sw, w, &s1);
+    const int x_lo = s0.start, x_hi = s1.end;
+    const int y_lo = spy[0].start;
+    int y_hi = spy[0].end;
+#pragma unroll
+    for (int r = 1; r < kServeRows; ++r)
+      if (r < nrow) y_hi = max(y_hi, spy[r].end);
+    const float okx = span_one_over_k(sw, w), oky = span_one_over_k(sh, h);
+    const uintptr_t F0 = reinterpret_cast<uintptr_t>(a.src) + (uintptr_t)f.offset;
+    const uintptr_t F1 = F0 + (uintptr_t)h * w * 3;
+    for (int y = y_lo; y < y_hi; ++y) {
+      float hrow[4] = {0.f, 0.f, 0.f, 0.f};  // the resized source row at this lane's elements
+      for (int x0 = x_lo; x0 < x_hi; x0 += kServeChunk) {
+        const int n = min(kServeChunk, x_hi - x0);
+        // bytes [A, A + 3n) of the frame, staged from the dword boundary A4 <= A
+        const uintptr_t A = F0 + ((uintptr_t)y * w + x0) * 3;
+        const uintptr_t A4 = A & ~(uintptr_t)3;
+        const int lead = (int)(A - A4);
+        const int nwords = (lead + 3 * n + 3) >> 2;
+        __syncthreads();  // the previous chunk has been read
+        for (int k = t; k < nwords; k += 256) {
+          const uintptr_t W = A4 + 4 * (uintptr_t)k;
+          // element q of the staged run is byte W + m; its channel is (q - lead) mod 3
+          int c = (4 * k - lead) % 3;
+          if (c < 0) c += 3;
+          float v[4];
+          if (W >= F0 && W + 4 <= F1) {
+            const uint32_t word = *reinterpret_cast<const uint32_t*>(W);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+              v[m] = tab[c * 256 + ((word >> (8 * m)) & 255u)];
+              c = c == 2 ? 0 : c + 1;
+            }
+          } else {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+              const uintptr_t p = W + m;
+              v[m] = (p >= F0 && p < F1) ? tab[c * 256 + *reinterpret_cast<const uint8_t*>(p)] : 0.f;
+              c = c == 2 ? 0 : c + 1;
+            }
+          }
+          *reinterpret_cast<float4*>(&row[4 * k]) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (!onx[j]) continue;
+          const int xa = max(spx[j].start, x0), xb = min(spx[j].end, x0 + n);
+          for (int x = xa; x < xb; ++x)
+            hrow[j] += span_weight(spx[j], x, okx) * row[lead + (x - x0) * 3 + cx[j]];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kServeRows; ++r) {
+        if (r < nrow && y >= spy[r].start && y < spy[r].end) {
+          const float wy = span_weight(spy[r], y, oky);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[r][j] += wy * hrow[j];
+        }
+      }
+    }
+  }
+  if (!lane_on) return;
+#pragma unroll
+  for (int r = 0; r < kServeRows; ++r) {
+    const int i = i0 + r;
+    if (i < S)
+      *reinterpret_cast<float4*>(a.images + ((long)b * S + i) * S * 3 + e0) =
+          make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+  }
+}
+
+void launch_serve_preprocess(const uint8_t* src, const ServeFrame* frames_dev, int B, int S, const float* mean,
+                             const float* stdv, float* images, float* scales, hipStream_t s) {
+  if ((S * 3) % 4) throw std::invalid_argument("serve_preprocess: image_size must be a multiple of 4");
+  ServePreArgs a;
+  a.src = src;
+  a.frames = frames_dev;
+  for (int c = 0; c < 3; ++c) {
+    a.mean[c] = mean[c];
+    a.std[c] = stdv[c];
+  }
+  a.S = S;
+  a.images = images;
+  a.scales = scales;
+  const dim3 grid((S * 3 + 1023) / 1024, (S + kServeRows - 1) / kServeRows, B);
+  hipLaunchKernelGGL(k_serve_pre, grid, dim3(256), 0, s, a);
+  PHX_LAUNCH_CHECK();
+}
+
+// classes = argmax + CLASS_OFFSET as float32 (postprocess.py:30, :402), boxes x image_scale_to_original
+// after the soft-NMS kernel's clip (:396-400); rows at and beyond the count are zero
+__global__ __launch_bounds__(128) void k_nms_global_epilogue(const int* __restrict__ sel, const int* __restrict__ count,
+                                                             const int* __restrict__ classes,
+                                                             const float* __restrict__ scales, int N, int max_out,
+                                                             float* __restrict__ boxes, float* __restrict__ out_classes) {
+  const int b = blockIdx.x;
+  const int n = count[b];
+  const float sc = scales ? scales[b] : 1.0f;
+  for (int k = threadIdx.x; k < max_out; k += blockDim.x) {
+    const long o = (long)b * max_out + k;
+    if (k < n) {
+      const int a = min(max(sel[o], 0), N - 1);
+      out_classes[o] = (float)(classes[(long)b * N + a] + 1);
+      if (scales) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) boxes[o * 4 + q] = boxes[o * 4 + q] * sc;
+      }
+    } else {
+      out_classes[o] = 0.f;
+    }
+  }
+}
+
+void launch_nms_global_epilogue(const int* sel, const int* count, const int* classes, const float* scales, int B,
+                                int N, int max_out, float* boxes, float* out_classes, hipStream_t s) {
+  hipLaunchKernelGGL(k_nms_global_epilogue, dim3(B), dim3(128), 0, s, sel, count, classes, scales, N, max_out, boxes,
+                     out_classes);
+  PHX_LAUNCH_CHECK();
+}
+
+}  // namespace phx

@@ -83,8 +83,9 @@ struct ModelConfig {
   float anchor_scale = 4.0f;
   int act = ACT_SWISH;
   int fpn_weight_method = 0;  // 0 fastattn, 1 sum
-  float mean_rgb[3] = {0.485f * 255, 0.456f * 255, 0.406f * 255};
-  float stddev_rgb[3] = {0.229f * 255, 0.224f * 255, 0.225f * 255};
+  // hparams_config.py:224-225: Python doubles, cast to float32 where the preprocess uses them
+  float mean_rgb[3] = {(float)(0.485 * 255), (float)(0.456 * 255), (float)(0.406 * 255)};
+  float stddev_rgb[3] = {(float)(0.229 * 255), (float)(0.224 * 255), (float)(0.225 * 255)};
   // backbone
   double width_coefficient = 1.0, depth_coefficient = 1.0;
   bool lite = false;             // relu6, no SE, fixed stem/head
