@@ -409,6 +409,49 @@ int phx_def_eval_step(phx_def* d, const float* images, int B, const float* boxes
                       const float* params, const float* eval_patch, float* metrics, float* out_boxes,
                       float* out_scores, int32_t* out_count, int64_t step, int32_t global_image_offset,
                       void* stream);
+/* ---- frame recovery (demo_v2.py:151-169 RecoveryDemo.serve, :133-134 run's uint8 cast) ----------
+ * The trained U-Net applied to raw frames.  For one uint8 RGB frame [h,w,3] at the victim's image size
+ * S with its mean_rgb / stddev_rgb:
+ *   x, scale = driver._preprocess(frame)            what phx_serve_preprocess writes (scale =
+ *                                                   image_scale_to_original, fp32)
+ *   y = clip(2 * PatchNeutralizer(x, training=False) + x, -1, 1) * stddev_rgb + mean_rgb   (fp32)
+ *   d = int(fp32(S) * scale)                        a truncating fp32 product
+ *   cv2.resize(y, (d, d))                           INTER_LINEAR on a CV_32FC3 source: fp32 weights
+ *                                                   (1 - f, f), f from float((o + .5) * (S / d) - .5)
+ *                                                   in double, taps clamped to the image, horizontal
+ *                                                   pass first; S == 2 d takes the 2x2 box mean
+ *   [:h, :w]                                        the float image serve returns; run then takes
+ *                                                   clip(., 0, 255).astype('uint8'), which truncates
+ * The recovered frame is (min(h, d), min(w, d)): the fp32 truncation can leave d one below the frame's
+ * longer side (50 x 211 -> 50 x 210, 90 x 120 -> 90 x 119), and the crop then returns a frame one row
+ * or column smaller than the input, as the reference does.
+ *
+ * phx_recover_dims: that size for B frames, host arithmetic only (no context, nothing launched):
+ * dims [B,2] int32 (h, w) -> out_dims [B,2] (min(h, d), min(w, d)).  PHX_EINVAL: a null pointer,
+ * image_size or B < 1, h or w < 1, a scaled side int(h * image_scale) or int(w * image_scale) of 0,
+ * d < 1 (tf.image.resize / cv2.resize raise there). */
+int phx_recover_dims(int image_size, const int32_t* dims, int B, int32_t* out_dims);
+/* The whole chain for a packed batch of frames, passed as for phx_serve (src device; offsets, dims
+ * host).  out_u8 (the clipped, truncated frame) and out_f32 (the float image) are packed device
+ * buffers, either may be NULL but not both; frame b starts at element out_offsets[b] (a HOST array,
+ * the same element offset in both buffers) and has phx_recover_dims' size, rows packed.  One kernel
+ * writes both, so out_u8 is exactly trunc(clip(out_f32, 0, 255)); nothing outside the frames is
+ * written.  params: the U-Net variables (phx_def_manifest order); inference BN from the moving
+ * statistics, no Dropout; no variable and no moving statistic changes, and the victim is not run.
+ * Every argument is checked on the host before anything is launched: PHX_EINVAL with a message naming
+ * the argument (phx_def_last_error) for B < 1, a null pointer, both outputs null, a negative offset
+ * and what phx_serve_preprocess refuses; PHX_ECAP for B > max_batch.  Runs on the caller's stream
+ * without synchronising; the host tables may be freed on return.  The first call reserves the frame
+ * tables and the first call at a batch size the workspace (both synchronous); later calls allocate
+ * nothing — unless 8 calls are still in flight, when the host waits for the oldest one's table.  Waits
+ * for a phx_def_set_next prefetch as phx_def_eval_step does and leaves it valid.
+ * The call reuses the training workspace: the preprocess writes the U-Net's input buffer and the
+ * output layer the `updates` buffer, so afterwards phx_def_debug(PHX_DEF_PATCHED / PHX_DEF_UPDATES)
+ * and phx_def_debug_tap show this call's canvas [B,S,S,3] and forward (PHX_DEF_TARGETS keeps the last
+ * step's). */
+int phx_def_recover(phx_def* d, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
+                    const float* params, uint8_t* out_u8, float* out_f32, const int64_t* out_offsets,
+                    void* stream);
 /* debug copies of the last step (device->device): patched images / targets / updates [B,H,W,3],
  * first-pass boxes [B,100,4], counts [B] (int32 bits) */
 enum { PHX_DEF_PATCHED = 0, PHX_DEF_TARGETS = 1, PHX_DEF_UPDATES = 2, PHX_DEF_BOXES = 3, PHX_DEF_COUNTS = 4 };

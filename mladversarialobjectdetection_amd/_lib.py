@@ -128,6 +128,10 @@ _SIGS = [
     ("phx_def_eval_step", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_int64, c_int, c_void_p]),
+    # frame recovery (offsets / dims / out_offsets are host arrays)
+    ("phx_recover_dims", c_int, [c_int, c_void_p, c_int, c_void_p]),
+    ("phx_def_recover", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_def_debug", c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     ("phx_def_debug_tap", c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]),
     ("phx_adam", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p]),

@@ -2363,6 +2363,26 @@ void serve_preprocess(phx_ctx* ctx, const uint8_t* src, const std::vector<ServeF
 
 }  // namespace
 
+// the defender's frame recovery (defender.cpp) preprocesses as phx_serve does
+extern "C++" {
+std::string phx::def_serve_frames(const phx_ctx* ctx, const char* fn, const void* src, const int64_t* offsets,
+                                  const int32_t* dims, int B, std::vector<ServeFrame>* out) {
+  return serve_frames(ctx, fn, src, offsets, dims, B, out);
+}
+
+void phx::def_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const std::vector<ServeFrame>& fr, float* images,
+                               float* scales, hipStream_t s) {
+  serve_preprocess(ctx, src, fr, images, scales, s);
+}
+
+void phx::ctx_mean_std(const phx_ctx* ctx, float mean[3], float stdv[3]) {
+  for (int c = 0; c < 3; ++c) {
+    mean[c] = ctx->mc.mean_rgb[c];
+    stdv[c] = ctx->mc.stddev_rgb[c];
+  }
+}
+}  // extern "C++"
+
 int phx_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
                          float* images, float* scales, void* stream) {
   if (!ctx) return PHX_EINVAL;

@@ -5,12 +5,15 @@
 //     updates = 2 * PatchNeutralizer(images)           generator.py:17-277 -> kernels_unet.hip + GEMM
 //     loss = sum_b mean((targets - updates)^2)         :194-198
 //     tape.gradient(loss, U-Net variables)             :202-206
+//   RecoveryDemo.serve (frame recovery)                  demo_v2.py:151-169 -> phx_def::recover: the serving
+//     preprocess into the U-Net's input, the inference-mode forward, k_def_recover (kernels_serve.hip)
 // The U-Net is hand-scheduled here (it is fixed: n_filters 8, four encoder blocks, a bottleneck,
 // four attention decoder blocks, a 1x1 tanh output); every tensor lives at a per-batch-size arena
 // offset, and the backward walks the same layers in reverse writing each variable's gradient once.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -111,6 +114,13 @@ struct phx_def {
       (void)hipStreamDestroy(side);
       (void)hipEventDestroy(ev_fork);
       (void)hipEventDestroy(ev_done);
+    }
+    if (rec_host) {
+      for (hipEvent_t e : rec_ev) {
+        (void)hipEventSynchronize(e);
+        (void)hipEventDestroy(e);
+      }
+      (void)hipHostFree(rec_host);
     }
   }
   // per batch-size workspace
@@ -250,13 +260,26 @@ struct phx_def {
   void prep_weights(const float* W, hipStream_t s);
   // U-Net forward on `patched` (train: batch-statistics BN with moving-statistics update and
   // Dropout; else inference BN from the moving statistics, no Dropout), then the output layer and
-  // loss against `mask` into *loss (and dz, its gradient)
+  // loss against `mask` into *loss (and dz, its gradient); loss == nullptr: no target, `upd` only
   void unet_forward(int B, const float* W, bool train, int64_t stp, int gimg0, float* loss, hipStream_t s);
   void step(const float* images, int B, const float* boxes_in, const int* count_in, const float* params,
             float* grad, int64_t step, int gimg0, hipStream_t s);
   void eval(const float* images, int B, const float* boxes_in, const int* count_in, const float* params,
             const float* eval_patch, float* metrics, float* out_boxes, float* out_scores, int* out_count,
             int64_t stp, int gimg0, hipStream_t s);
+  // frame recovery (phx_def_recover): image_scale_to_original [max_batch] and the epilogue's frame
+  // tables, a ring like the victim's serving ring (kRecRing slots of max_batch frames, pinned on the
+  // host and mirrored on the device; a call fills the next slot, copies it on its stream and records
+  // the slot's event after the epilogue).  Reserved by the first recovery, kept until destruction.
+  static constexpr int kRecRing = 8;
+  DBuf rec_scales, rec_dev;
+  RecFrame* rec_host = nullptr;
+  hipEvent_t rec_ev[kRecRing] = {};
+  bool rec_busy[kRecRing] = {};
+  int rec_next = 0;
+  const RecFrame* rec_stage(const std::vector<RecFrame>& fr, hipStream_t s, int* slot_out);
+  void recover(const uint8_t* src, const std::vector<ServeFrame>& fr, const std::vector<RecFrame>& rf,
+               const float* params, uint8_t* out_u8, float* out_f32, hipStream_t s);
 };
 
 namespace {
@@ -505,7 +528,8 @@ void phx_def::unet_forward(int B, const float* W, bool train, int64_t stp, int g
   const long Mf = (long)B * S * S;
   const UConv& oc = convs[out_conv];
   DScope g(victim, "unet_other", 2.0 * Mf * 3 * oc.ci, 4.0 * Mf * (oc.ci + 9), s);
-  un_out_loss(x, W + oc.w, W + oc.b, mask, upd, dz, lpart, loss, Mf, (long)S * S, oc.ci, s);
+  if (loss) un_out_loss(x, W + oc.w, W + oc.b, mask, upd, dz, lpart, loss, Mf, (long)S * S, oc.ci, s);
+  else un_out(x, W + oc.w, W + oc.b, upd, Mf, oc.ci, s);
   fwdB = B;
 }
 
@@ -740,6 +764,84 @@ void phx_def::eval(const float* images, int B, const float* boxes_in, const int*
   unet_forward(B, W, false, stp, gimg0, metrics, s);
 }
 
+namespace {
+
+// The recovered frame's size (demo_v2.py:157-168) by the reference's fp32 rules: image_scale =
+// min(fp32(S) / h, fp32(S) / w) and the scaled sides as DetectionInputProcessor's (dataloader.py:115-127),
+// scale = image_scale_to_original = 1 / image_scale, d = int(fp32(S) * scale), output [:h, :w] of the
+// d x d resize.  Returns the refusal's reason ("" = fine).
+std::string recover_size(int S, int h, int w, RecFrame* out) {
+  if (h < 1 || w < 1) return "h and w must be >= 1";
+  const float sc = std::fmin((float)S / (float)h, (float)S / (float)w);
+  if ((int)((float)h * sc) < 1) return "scaled height int(h * image_scale) is 0";
+  if ((int)((float)w * sc) < 1) return "scaled width int(w * image_scale) is 0";
+  const float inv = 1.0f / sc;
+  const float df = (float)S * inv;  // a truncating fp32 product
+  if (!(df >= 1.0f)) return "recovered side int(image_size * image_scale_to_original) is 0";
+  if (df >= 2147483648.0f) return "recovered side exceeds the int range";
+  const int d = (int)df;
+  *out = RecFrame{0, std::min(h, d), std::min(w, d), d, 0, 1.0 / ((double)d / (double)S)};
+  return "";
+}
+
+}  // namespace
+
+// the next slot of the recovery frame-table ring, filled and copied on `s` (the victim's serve_stage)
+const RecFrame* phx_def::rec_stage(const std::vector<RecFrame>& fr, hipStream_t s, int* slot_out) {
+  const size_t slot_frames = (size_t)max_batch;
+  if (!rec_host) {
+    const size_t n = slot_frames * kRecRing;
+    void* p = nullptr;
+    PHX_HIP(hipMalloc(&p, (size_t)max_batch * sizeof(float)));
+    rec_scales.reset(p);
+    PHX_HIP(hipMalloc(&p, n * sizeof(RecFrame)));
+    rec_dev.reset(p);
+    for (hipEvent_t& e : rec_ev) PHX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    PHX_HIP(hipHostMalloc(&p, n * sizeof(RecFrame), hipHostMallocDefault));
+    rec_host = static_cast<RecFrame*>(p);
+  }
+  const int slot = rec_next;
+  rec_next = (slot + 1) % kRecRing;
+  if (rec_busy[slot]) PHX_HIP(hipEventSynchronize(rec_ev[slot]));  // kRecRing calls in flight
+  rec_busy[slot] = false;
+  RecFrame* h = rec_host + slot * slot_frames;
+  RecFrame* dv = static_cast<RecFrame*>(rec_dev.get()) + slot * slot_frames;
+  std::memcpy(h, fr.data(), fr.size() * sizeof(RecFrame));
+  PHX_HIP(hipMemcpyAsync(dv, h, fr.size() * sizeof(RecFrame), hipMemcpyHostToDevice, s));
+  *slot_out = slot;
+  return dv;
+}
+
+// RecoveryDemo.serve (demo_v2.py:151-169) and run's uint8 cast (:134): the serving preprocess straight
+// into the U-Net's input buffer, the inference-mode forward with the target-less output layer, and one
+// epilogue launch for the whole batch.  Neither the victim nor the Masker runs; nothing is updated.
+void phx_def::recover(const uint8_t* src, const std::vector<ServeFrame>& fr, const std::vector<RecFrame>& rf,
+                      const float* W, uint8_t* out_u8, float* out_f32, hipStream_t s) {
+  const int B = (int)fr.size();
+  workspace(B);
+  int slot = 0;
+  const RecFrame* table = rec_stage(rf, s, &slot);
+  join(s);  // (a prefetched first pass stays valid: this call only shares the victim's frame-table ring)
+  prep_weights(W, s);
+  def_serve_preprocess(victim, src, fr, patched, static_cast<float*>(rec_scales.get()), s);
+  unet_forward(B, W, false, 0, 0, nullptr, s);
+  float mean[3], stdv[3];
+  ctx_mean_std(victim, mean, stdv);
+  long max_elems = 0;
+  double bytes = 0;
+  for (const RecFrame& f : rf) {
+    const long n = (long)f.oh * f.ow * 3;
+    max_elems = std::max(max_elems, n);
+    bytes += 24.0 * S * S + (double)n * ((out_u8 ? 1 : 0) + (out_f32 ? 4 : 0));
+  }
+  {
+    DScope g(victim, "recover_epilogue", 0.0, bytes, s);
+    launch_def_recover(patched, upd, table, B, S, mean, stdv, out_u8, out_f32, max_elems, s);
+  }
+  PHX_HIP(hipEventRecord(rec_ev[slot], s));
+  rec_busy[slot] = true;
+}
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -889,6 +991,53 @@ int phx_def_eval_step(phx_def* d, const float* images, int B, const float* boxes
   PHX_HIP(hipSetDevice(d->device));
   d->eval(images, B, boxes, count, params, eval_patch, metrics, out_boxes, out_scores, out_count, step,
           global_image_offset, (hipStream_t)stream);
+  return PHX_OK;
+  DEF_CATCH(d)
+}
+
+int phx_recover_dims(int image_size, const int32_t* dims, int B, int32_t* out_dims) {
+  if (image_size < 1 || !dims || !out_dims || B < 1) return PHX_EINVAL;
+  for (int b = 0; b < B; ++b) {
+    RecFrame f;
+    if (!recover_size(image_size, dims[2 * b], dims[2 * b + 1], &f).empty()) return PHX_EINVAL;
+    out_dims[2 * b] = f.oh;
+    out_dims[2 * b + 1] = f.ow;
+  }
+  return PHX_OK;
+}
+
+int phx_def_recover(phx_def* d, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
+                    const float* params, uint8_t* out_u8, float* out_f32, const int64_t* out_offsets, void* stream) {
+  if (!d) return PHX_EINVAL;
+  // every check is host arithmetic: a refused call has launched nothing
+  auto refuse = [&](int code, const std::string& msg) {
+    d->err = "def_recover: " + msg;
+    return code;
+  };
+  if (B < 1) return refuse(PHX_EINVAL, "B = " + std::to_string(B) + " must be >= 1");
+  if (B > d->max_batch)
+    return refuse(PHX_ECAP, "B = " + std::to_string(B) + " exceeds max_batch = " + std::to_string(d->max_batch));
+  if (!params) return refuse(PHX_EINVAL, "params is null");
+  if (!out_u8 && !out_f32) return refuse(PHX_EINVAL, "out_u8 and out_f32 are both null");
+  if (!out_offsets) return refuse(PHX_EINVAL, "out_offsets is null");
+  if (reinterpret_cast<uintptr_t>(out_f32) & 3) return refuse(PHX_EINVAL, "out_f32 is not 4-byte aligned");
+  std::vector<ServeFrame> fr;
+  const std::string bad = def_serve_frames(d->victim, "def_recover", src, offsets, dims, B, &fr);
+  if (!bad.empty()) {
+    d->err = bad;
+    return PHX_EINVAL;
+  }
+  std::vector<RecFrame> rf((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const std::string at = "dims[" + std::to_string(b) + "] = " + std::to_string(fr[b].h) + "x" + std::to_string(fr[b].w);
+    const std::string why = recover_size(d->S, fr[b].h, fr[b].w, &rf[b]);
+    if (!why.empty()) return refuse(PHX_EINVAL, at + ": " + why);
+    if (out_offsets[b] < 0) return refuse(PHX_EINVAL, "out_offsets[" + std::to_string(b) + "] is negative");
+    rf[b].out_off = out_offsets[b];
+  }
+  DEF_TRY
+  PHX_HIP(hipSetDevice(d->device));
+  d->recover(src, fr, rf, params, out_u8, out_f32, (hipStream_t)stream);
   return PHX_OK;
   DEF_CATCH(d)
 }

@@ -397,6 +397,20 @@ void launch_serve_preprocess(const uint8_t* src, const ServeFrame* frames_dev, i
 // float, boxes *= scales[b] (scales may be null); rows >= count[b] get class 0
 void launch_nms_global_epilogue(const int* sel, const int* count, const int* classes, const float* scales, int B,
                                 int N, int max_out, float* boxes, float* out_classes, hipStream_t s);
+// one frame of a recovery call (demo_v2.py:151-169), sized on the host
+struct RecFrame {
+  int64_t out_off;  // element offset of the recovered frame in out_u8 / out_f32
+  int oh, ow;       // min(h, d), min(w, d): the cropped region, the only part computed
+  int d;            // int(fp32(S) * image_scale_to_original): cv2.resize's destination side
+  int pad_;
+  double scale;     // cv2's source step per destination pixel, 1 / (d / S) in double
+};
+// recovery epilogue over canvas / updates [B,S,S,3]: per tap clip(u + x, -1, 1) * std + mean, then
+// cv2.resize INTER_LINEAR (CV_32F) to d x d cropped to oh x ow, into out_f32 and / or the clipped,
+// truncated out_u8 (either may be null); max_elems = the largest oh * ow * 3 of the batch
+void launch_def_recover(const float* canvas, const float* updates, const RecFrame* frames_dev, int B, int S,
+                        const float* mean, const float* stdv, uint8_t* out_u8, float* out_f32, long max_elems,
+                        hipStream_t s);
 // flip -> RandomFlip -> RandomContrast(.2) -> random_brightness(.2) -> clip; in/out [B,H,W,3]
 size_t augment_scratch_doubles(int B);
 void launch_augment(const float* in, float* out, int B, int H, int W, uint64_t seed, int64_t step,

@@ -5,6 +5,8 @@
 //                tf.image.resize(antialias=True) + pad_to_bounding_box, :199-201 image_scale_to_original)
 //   epilogue     postprocess_global's class gather and rescale (postprocess.py:375-406) after the
 //                soft-NMS kernel, which has clipped the boxes to [0, S] (clip_boxes, :61-64)
+//   recovery     RecoveryDemo.serve after the U-Net (demo_v2.py:159-168): add, clip, denormalise,
+//                cv2.resize back to frame scale and crop (k_def_recover, below the serving kernels)
 //
 // k_serve_pre: one launch for a packed batch of uint8 frames of any sizes, no intermediate tensor in
 // HBM.  A workgroup owns kServeRows canvas rows x 1024 consecutive canvas floats (256 lanes x one
@@ -206,6 +208,159 @@ void launch_nms_global_epilogue(const int* sel, const int* count, const int* cla
                                 int N, int max_out, float* boxes, float* out_classes, hipStream_t s) {
   hipLaunchKernelGGL(k_nms_global_epilogue, dim3(B), dim3(128), 0, s, sel, count, classes, scales, N, max_out, boxes,
                      out_classes);
+  PHX_LAUNCH_CHECK();
+}
+
+// ---- recovery epilogue (demo_v2.py:159-168) ----------------------------------------------------------
+// k_def_recover: one launch for a batch of differently sized frames, no [S,S,3] or [d,d,3] intermediate
+// in HBM.  A frame's cropped output [oh,ow,3] is one contiguous run of oh * ow * 3 elements; a lane owns
+// four consecutive ones, cut so that its uint8 store is one aligned dword (its float store one aligned
+// 16-B word when that address allows, else four dwords), a wave's stores are contiguous.  Every element
+// takes its four taps from the canvas and `updates` (1.5 MB each per image at S = 512: they stay in
+// L2), applies add, clip and denormalise per tap in fp32 (each multiply and add rounds on its own, as
+// numpy's), then interpolates as cv2's CV_32F resize does: horizontal pass first, fp32 weights (1 - f, f)
+// with f from the double expression, taps clamped.  S == 2 d is cv2's INTER_AREA shortcut, the 2x2
+// box sum times 0.25.  Algorithmic bytes per frame: 24 * S * S read + (4 and / or 1) * oh * ow * 3 written.
+struct RecoverArgs {
+  const float* canvas;
+  const float* upd;
+  const RecFrame* frames;
+  float mean[3], std[3];
+  int S;
+  uint8_t* out_u8;
+  float* out_f32;
+};
+
+struct RecAxis {
+  int i0, i1;
+  float w0, w1;
+};
+
+// cv2's resize tables for destination index o (resize.cpp: fx = (float)((dx + 0.5) * scale_x - 0.5);
+// sx = cvFloor(fx); fx -= sx): the horizontal table resets the weight where it clamps, the vertical
+// pass clamps the rows and keeps the weights
+__device__ __forceinline__ RecAxis rec_axis(int o, double scale, int S, bool horizontal) {
+  float f = (float)(((double)o + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f -= (float)s;
+  RecAxis a;
+  if (horizontal) {
+    if (s < 0) {
+      s = 0;
+      f = 0.f;
+    }
+    if (s >= S - 1) {
+      s = S - 1;
+      f = 0.f;
+    }
+    a.i0 = s;
+    a.i1 = min(s + 1, S - 1);
+  } else {
+    a.i0 = min(max(s, 0), S - 1);
+    a.i1 = min(max(s + 1, 0), S - 1);
+  }
+  a.w0 = 1.0f - f;
+  a.w1 = f;
+  return a;
+}
+
+// clip(2 * PatchNeutralizer(x) + x, -1, 1) * stddev_rgb + mean_rgb at one canvas element
+__device__ __forceinline__ float rec_tap(const float* __restrict__ cv, const float* __restrict__ up, long i, float sd,
+                                         float mn) {
+  const float y = fminf(fmaxf(up[i] + cv[i], -1.0f), 1.0f);
+  return y * sd + mn;
+}
+
+__global__ __launch_bounds__(256) void k_def_recover(RecoverArgs a) {
+  const int b = blockIdx.y;
+  const RecFrame f = a.frames[b];
+  const int S = a.S;
+  const long row = (long)f.ow * 3, n = row * f.oh;
+  // lane groups start `pad` elements before the frame so that group stores are aligned words
+  const int pad = a.out_u8 ? (int)(reinterpret_cast<uintptr_t>(a.out_u8 + f.out_off) & 3)
+                           : (int)((reinterpret_cast<uintptr_t>(a.out_f32 + f.out_off) >> 2) & 3);
+  const long e0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4 - pad;
+  if (e0 >= n) return;
+  const long ef = e0 < 0 ? 0 : e0;
+  int oy = (int)(ef / row);
+  const int r = (int)(ef - (long)oy * row);
+  int ox = r / 3, c = r - ox * 3;
+  const float* __restrict__ cv = a.canvas + (long)b * S * S * 3;
+  const float* __restrict__ up = a.upd + (long)b * S * S * 3;
+  const bool box = 2 * f.d == S;
+  RecAxis ay = rec_axis(oy, f.scale, S, false), ax = rec_axis(ox, f.scale, S, true);
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long e = e0 + j;
+    v[j] = 0.f;
+    if (e < 0 || e >= n) continue;
+    const float sd = c == 0 ? a.std[0] : c == 1 ? a.std[1] : a.std[2];
+    const float mn = c == 0 ? a.mean[0] : c == 1 ? a.mean[1] : a.mean[2];
+    const long r0 = (long)ay.i0 * S * 3 + c, r1 = (long)ay.i1 * S * 3 + c;
+    const float t00 = rec_tap(cv, up, r0 + ax.i0 * 3, sd, mn), t01 = rec_tap(cv, up, r0 + ax.i1 * 3, sd, mn);
+    const float t10 = rec_tap(cv, up, r1 + ax.i0 * 3, sd, mn), t11 = rec_tap(cv, up, r1 + ax.i1 * 3, sd, mn);
+    if (box) {
+      v[j] = (((t00 + t01) + t10) + t11) * 0.25f;
+    } else {
+      const float h0 = t00 * ax.w0 + t01 * ax.w1, h1 = t10 * ax.w0 + t11 * ax.w1;
+      v[j] = h0 * ay.w0 + h1 * ay.w1;
+    }
+    if (++c == 3) {
+      c = 0;
+      if (++ox == f.ow) {
+        ox = 0;
+        ay = rec_axis(++oy, f.scale, S, false);
+      }
+      ax = rec_axis(ox, f.scale, S, true);
+    }
+  }
+  const bool full = e0 >= 0 && e0 + 4 <= n;
+  if (a.out_f32) {
+    float* p = a.out_f32 + f.out_off + e0;
+    if (full && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+      *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j >= 0 && e0 + j < n) p[j] = v[j];
+    }
+  }
+  if (a.out_u8) {
+    // np.clip(., 0, 255).astype('uint8') (demo_v2.py:134): the cast truncates
+    uint32_t q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = (uint32_t)(int)fminf(fmaxf(v[j], 0.f), 255.f);
+    uint8_t* p = a.out_u8 + f.out_off + e0;
+    if (full) {  // (dword aligned by the choice of pad)
+      *reinterpret_cast<uint32_t*>(p) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j >= 0 && e0 + j < n) p[j] = (uint8_t)q[j];
+    }
+  }
+}
+
+void launch_def_recover(const float* canvas, const float* updates, const RecFrame* frames_dev, int B, int S,
+                        const float* mean, const float* stdv, uint8_t* out_u8, float* out_f32, long max_elems,
+                        hipStream_t s) {
+  if (!out_u8 && !out_f32) throw std::invalid_argument("def_recover: no output");
+  if (B < 1 || S < 2 || max_elems < 1) throw std::invalid_argument("def_recover: empty batch or frame");
+  RecoverArgs a;
+  a.canvas = canvas;
+  a.upd = updates;
+  a.frames = frames_dev;
+  for (int c = 0; c < 3; ++c) {
+    a.mean[c] = mean[c];
+    a.std[c] = stdv[c];
+  }
+  a.S = S;
+  a.out_u8 = out_u8;
+  a.out_f32 = out_f32;
+  const long groups = (max_elems + 3 + 3) / 4;  // up to 3 elements of lead-in per frame
+  const dim3 grid((unsigned)((groups + 255) / 256), B);
+  hipLaunchKernelGGL(k_def_recover, grid, dim3(256), 0, s, a);
   PHX_LAUNCH_CHECK();
 }
 

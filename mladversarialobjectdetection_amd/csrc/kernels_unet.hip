@@ -832,6 +832,21 @@ __global__ __launch_bounds__(256) void k_un_out_loss(const float* __restrict__ x
   if (threadIdx.x == 0) lpart[blockIdx.x] = sh[0];
 }
 
+// the output layer without a target (frame recovery): u = 2 tanh(x W + b) only, the same sums in the
+// same order as k_un_out_loss, so `upd` is bit for bit what that kernel stores
+__global__ __launch_bounds__(256) void k_un_out(const float* __restrict__ x, const float* __restrict__ w,
+                                                const float* __restrict__ bias, float* __restrict__ upd, long M,
+                                                int C) {
+  for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+      float z = bias[o];
+      for (int c = 0; c < C; ++c) z = fmaf(x[m * C + c], w[c * 3 + o], z);
+      upd[m * 3 + o] = 2.0f * tanhf(z);
+    }
+  }
+}
+
 __global__ void k_un_loss_final(const double* __restrict__ lpart, int n, float* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double s = 0.0;
@@ -1126,6 +1141,11 @@ void un_out_loss(const float* x, const float* w, const float* b, const float* tg
   hipLaunchKernelGGL(k_un_out_loss, dim3(nb), dim3(256), 0, st, x, w, b, tgt, upd, dz, lpart, M, HW, C);
   PHX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_un_loss_final, dim3(1), dim3(64), 0, st, lpart, nb, loss);
+  PHX_LAUNCH_CHECK();
+}
+
+void un_out(const float* x, const float* w, const float* b, float* upd, long M, int C, hipStream_t st) {
+  hipLaunchKernelGGL(k_un_out, dim3(un_loss_blocks(M)), dim3(256), 0, st, x, w, b, upd, M, C);
   PHX_LAUNCH_CHECK();
 }
 

@@ -4,10 +4,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
+#include <vector>
 
 struct phx_ctx;
 
 namespace phx {
+
+struct ServeFrame;  // kernels.hpp
 
 // ---- gathers and weight matrices (kernels_unet.hip) ----------------------------------------
 // col [B*Ho*Wo, Kp]: mode 0 conv (stride s, pads pt / pl), mode 1 transposed conv (stride 2)
@@ -61,6 +65,8 @@ void un_att_s_bwd(const float* dt, const float* w3, const float* g, const float*
 int un_loss_blocks(long M);
 void un_out_loss(const float* x, const float* w, const float* b, const float* tgt, float* upd, float* dz,
                  double* lpart, float* loss, long M, long HW, int C, hipStream_t st);
+// the output layer alone, upd = 2 tanh(x W + b): no target, no loss partials, no dz
+void un_out(const float* x, const float* w, const float* b, float* upd, long M, int C, hipStream_t st);
 void un_small_dgrad(const float* dz, const float* w, float* dx, long M, int C, int O, bool acc, hipStream_t st);
 void un_add(float* a, const float* b, long n, hipStream_t st);
 
@@ -98,5 +104,13 @@ int ctx_device(const phx_ctx* ctx);
 // version (bumped by every load and training pass) and the score thresholds — a prefetched first pass
 // made at another generation is stale
 uint64_t ctx_generation(const phx_ctx* ctx);
+// the serving preprocess on the victim's context, for frame recovery: phx_serve_preprocess's argument
+// checks and frame table (host arithmetic only; returns the first bad argument's message, "" = fine),
+// the launch itself (through the context's frame-table ring), and the model's mean_rgb / stddev_rgb
+std::string def_serve_frames(const phx_ctx* ctx, const char* fn, const void* src, const int64_t* offsets,
+                             const int32_t* dims, int B, std::vector<ServeFrame>* out);
+void def_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const std::vector<ServeFrame>& fr, float* images,
+                          float* scales, hipStream_t s);
+void ctx_mean_std(const phx_ctx* ctx, float mean[3], float stdv[3]);
 
 }  // namespace phx

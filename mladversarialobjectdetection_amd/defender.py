@@ -150,6 +150,17 @@ def unet_tap_shapes(S: int, B: int, nf: int = 8) -> dict:
     return out
 
 
+def recovered_dims(image_size: int, dims) -> np.ndarray:
+    """phx_recover_dims: the (h', w') of the recovered frames of [B,2] (h, w) frames at the victim's
+    image size (host arithmetic; a size the reference's resizes would refuse raises)."""
+    dims = np.ascontiguousarray(dims, np.int32).reshape(-1, 2)
+    out = np.empty_like(dims)
+    rc = _lib.load().phx_recover_dims(int(image_size), dims.ctypes.data, len(dims), out.ctypes.data)
+    if rc != 0:
+        raise _lib.PhxError(f"phx_recover_dims failed ({rc}): image_size {image_size}, frames {dims.tolist()}")
+    return out
+
+
 class PatchAttackDefender:
     """attack_detection.PatchAttackDefender (training path): the protege is frozen (inference BN),
     the trainable variables are the U-Net's."""
@@ -307,6 +318,31 @@ class PatchAttackDefender:
         preds = self.call(inputs, training=False, boxes=boxes)
         ddp.allreduce_sum_(self.eval_loss)
         return {"loss": float(self.eval_loss.item())}, preds
+
+    def recover(self, frames, *, uint8=True, float32=False):
+        """RecoveryDemo.serve (demo_v2.py:151-169) and run's uint8 cast (:134) for a batch of raw uint8
+        frames (anything detector.pack_frames takes) through one phx_def_recover call: preprocess, the
+        U-Net in inference mode, clip(2 * PatchNeutralizer(x) + x, -1, 1), denormalise, cv2.resize back
+        to frame scale, crop.  -> (recovered, floats): `recovered` a detector.PackedFrames of the
+        clipped, truncated uint8 frames on the device (None when uint8=False), `floats` the float
+        images as one packed float32 device tensor (None unless float32=True) with the same element
+        offsets and sizes (recovered_dims gives them without a call).  A recovered frame can be one row
+        or column smaller than its input (phx.h)."""
+        from .detector import PackedFrames, pack_frames
+        p = pack_frames(frames, self.params.device)
+        B = len(p.offsets)
+        dims = recovered_dims(self.protege_model.ctx.image_size, p.dims)
+        sizes = dims[:, 0].astype(np.int64) * dims[:, 1] * 3
+        # frames start at multiples of 16 elements: whole-word stores in both outputs
+        offsets = np.zeros(B, np.int64)
+        offsets[1:] = np.cumsum((sizes + 15) // 16 * 16)[:-1]
+        total = int(offsets[-1] + sizes[-1])
+        u8 = torch.empty(total, dtype=torch.uint8, device=p.src.device) if uint8 else None
+        f32 = torch.empty(total, dtype=torch.float32, device=p.src.device) if float32 else None
+        self.handle.call("phx_def_recover", p.src.data_ptr(), p.offsets.ctypes.data, p.dims.ctypes.data, B,
+                         self.params.data_ptr(), u8.data_ptr() if uint8 else None,
+                         f32.data_ptr() if float32 else None, offsets.ctypes.data, _stream())
+        return (PackedFrames(u8, offsets, dims) if uint8 else None), f32
 
     def debug(self, what: int, B: int):
         S = self.protege_model.ctx.image_size
