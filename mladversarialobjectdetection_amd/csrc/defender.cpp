@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 #include "phx.h"
 #include "post.hpp"
@@ -300,8 +301,7 @@ void gemm(const float* A, const float* Bt, const float* bias, float* C, long M, 
 // PHX_UN_GATHER=0: the U-Net's wide 3x3 convs write their column matrix (k_im2col) and run the plain
 // GEMM over it instead of gathering it inside the GEMM (read on every call: tests compare the two)
 bool un_gather_on() {
-  const char* e = std::getenv("PHX_UN_GATHER");
-  return !(e && e[0] == '0');
+  return env_on("PHX_UN_GATHER");
 }
 
 // a 3x3 conv of more than kConvMaxN outputs (or K > kConvMaxKp): the GEMM over the gathered column

@@ -9,6 +9,7 @@
 // Reference ops: Conv2D / DepthwiseConv2dNative with TF 'SAME' padding
 // (efficientnet_model.py:305-359, 512-520; efficientdet_keras.py:196-207, 249-253, 387-411).
 #include "common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -1023,10 +1024,7 @@ size_t gemm_partial_floats(int M, int N, int K, bool bf16) {
 // which GEMM implementation launch_gemm / launch_gemm_dgrad use: PHX_GEMM=1 (16x16x4 register
 // kernel) or 2 (LDS-tiled persistent 32x32x2 kernel, default); PHX_GEMM_WGS: persistent width
 static int gemm_impl_env() {
-  static int v = [] {
-    const char* e = getenv("PHX_GEMM");
-    return e ? atoi(e) : 0;
-  }();
+  static int v = (int)env_long("PHX_GEMM", 0);
   return v;
 }
 // default (0): the 32x32 LDS-tiled kernel except for 16-wide outputs, where its 32-column tile
@@ -1038,10 +1036,7 @@ int gemm_impl_for(int N, bool) {
 }
 int gemm_impl() { return gemm_impl_env() ? gemm_impl_env() : 2; }
 int gemm2_target_wgs() {
-  static int v = [] {
-    const char* e = getenv("PHX_GEMM_WGS");
-    return e ? atoi(e) : 1024;
-  }();
+  static int v = (int)env_long("PHX_GEMM_WGS", 1024);
   return v;
 }
 

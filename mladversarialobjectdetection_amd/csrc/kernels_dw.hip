@@ -24,6 +24,7 @@
 #include <stdexcept>
 #include <type_traits>
 
+#include "env.hpp"
 #include "dw_stage.hpp"
 #include "kernels.hpp"
 
@@ -554,10 +555,7 @@ int launch_dw_fwd(InX x, const float* w, float* y, int B, int H, int W, int C, i
 // columns), and this launch has no statistics, so the outputs are bit-identical.
 // g: the ordinary (four rows per lane) plan of the launch
 static bool dw_fused_small(int B, const DwGeom& g) {
-  static const long small_below = [] {
-    const char* e = std::getenv("PHX_DW_FUSE_SMALL");  // workgroup count below which (0: off)
-    return e ? std::atol(e) : 512L;
-  }();
+  static const long small_below = env_long("PHX_DW_FUSE_SMALL", 512L);  // workgroup count below which (0: off)
   return (long)B * g.ntiles * g.ncg < small_below;
 }
 

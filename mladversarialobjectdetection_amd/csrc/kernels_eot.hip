@@ -16,6 +16,7 @@
 //     weights normalised) with its exact adjoint in the backward.
 // Ops that decide discrete geometry follow TF's fp32 operation order with FMA contraction off.
 #include "common.hpp"
+#include "env.hpp"
 #include "post.hpp"
 
 #pragma clang fp contract(off)
@@ -58,8 +59,7 @@ constexpr int kResizeRT = 4;
 // PHX_EOT_V1=1: the round-4 composite and resize-adjoint kernels (A/B and the bit-identity test;
 // read per call)
 static bool eot_v1() {
-  const char* e = std::getenv("PHX_EOT_V1");
-  return e && e[0] == '1';
+  return env_flag("PHX_EOT_V1");
 }
 
 __global__ __launch_bounds__(256) void k_eot_place(EotDims d, const float* __restrict__ boxes,

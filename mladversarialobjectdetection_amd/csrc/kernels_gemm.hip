@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "env.hpp"
 #include "gemm2_kernel.hpp"
 
 namespace phx {
@@ -50,10 +51,7 @@ static G2Cfg g2_pick(int N, int K, bool bf16) {
   if (N <= 96) return {4, 1, 3};
   if (N <= 128) return {2, 2, 2};
   if (N <= 160) return {4, 1, 5};
-  static const bool waste = [] {
-    const char* e = std::getenv("PHX_G2PICK");
-    return !(e && e[0] == '0');
-  }();
+  static const bool waste = env_on("PHX_G2PICK");
   if (waste && !bf16) {  // fp32 only: the bf16 tiles measured slightly slower with it (D4 C4)
     if (N % 128 != 0 && N % 96 == 0) return {4, 1, 3};
     if (N % 128 != 0 && N % 160 == 0) return {4, 1, 5};
@@ -121,16 +119,10 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
   }
   // few 128x128 tiles (small M, wide N, no split-K): 64-row tiles double the workgroups so
   // every CU gets MFMA work
-  static const bool half_rows = [] {
-    const char* e = std::getenv("PHX_G212");
-    return !(e && e[0] == '0');
-  }();
+  static const bool half_rows = env_on("PHX_G212");
   if (half_rows) {
     auto wgs = [&](const G2Cfg& q) { return (long)cdiv(M, q.bm()) * cdiv(N, q.bn()); };
-    static const bool tiles_first = [] {
-      const char* e = std::getenv("PHX_TILES_FIRST");
-      return e && e[0] == '1';
-    }();
+    static const bool tiles_first = env_flag("PHX_TILES_FIRST");
     auto halve = [&](G2Cfg q, int Mx) {
       auto wgx = [&](const G2Cfg& r) { return (long)cdiv(Mx, r.bm()) * cdiv(N, r.bn()); };
       const bool splits = !tiles_first && wgx(q) < 256 && K >= 256;  // split-K covers these
@@ -150,10 +142,7 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
   p.gy = cdiv(N, c.bn());
   const long tiles = (long)p.mtiles * p.gy;
   p.splits = 1;
-  static const long split_below = [] {
-    const char* e = std::getenv("PHX_SPLIT_TILES");
-    return e ? std::atol(e) : 256L;
-  }();
+  static const long split_below = env_long("PHX_SPLIT_TILES", 256L);
   if (tiles < split_below && K >= 256)
     p.splits = std::max(1, std::min<int>((int)((2 * split_below + tiles - 1) / tiles), K / 128));
   const int bk = bf16 ? PHX_GEMM_BK_BF16 : PHX_GEMM_BK_F32;  // K chunk of the kernel variant
@@ -161,19 +150,13 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
   p.splits = (K + p.kslice - 1) / p.kslice;
   // deep K over few tiles: split K across the waves of a workgroup instead (k_gemm2k; PHX_GEMM_WSK=0
   // keeps the cross-workgroup split)
-  static const bool wsk_on = [] {
-    const char* e = std::getenv("PHX_GEMM_WSK");
-    return !(e && e[0] == '0');
-  }();
+  static const bool wsk_on = env_on("PHX_GEMM_WSK");
   // the bf16 compute type takes k_gemm2k too (C4 27.80 -> 27.52-27.59 ms; PHX_GEMM_WSK_BF16=0 keeps the
   // split).  Its first affected layer differs from the split kernels' in 8e-5 of the stored bf16
   // values, each by one quantum (fp32 summation order); deeper, both builds are draws of the same
   // bf16 storage noise, equally far from the emulation oracle ("bf16 wave-split-K,
   // diagnosed"; scripts/diag_bf16_wsk_layers.py)
-  static const bool wsk_bf16 = [] {
-    const char* e = std::getenv("PHX_GEMM_WSK_BF16");
-    return !(e && e[0] == '0');
-  }();
+  static const bool wsk_bf16 = env_on("PHX_GEMM_WSK_BF16");
   // bf16: the A view (fp32 VALU, once per N tile) outweighs the cheap bf16 MFMAs, so a split tile that
   // spans all of N exactly (one view pass: N = 160 on 128x160) stays faster than the narrower
   // wave-split tiles (tools/gemm_bench GEMM_WSK sweeps, D4 shapes)
@@ -187,10 +170,7 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
   // kept it off for a metric-row bound that was tighter than the per-image bound it sums (DESIGN.md
   // section 5); with check_metric_row's bounds derived from the per-image ones it is on (PHX_GEMM_WSK_SMALL=0
   // turns it off)
-  static const bool wsk_small = [] {
-    const char* e = std::getenv("PHX_GEMM_WSK_SMALL");
-    return !(e && e[0] == '0');
-  }();
+  static const bool wsk_small = env_on("PHX_GEMM_WSK_SMALL");
   // splits / few as this function finds them for Mi rows (= p.splits and the tile count when Mi == M)
   const long tiles_i = (long)cdiv(Mi, ci.bm()) * cdiv(N, ci.bn());
   int splits_i = 1;
@@ -223,20 +203,14 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16, bool allow_
   // with several N tiles, a multiple of 8 workgroups along M puts the gy workgroups that stream
   // the same A rows on one XCD (dispatch is round-robin over the 8 XCDs), so A is read from HBM
   // once per XCD L2 instead of once per N tile
-  static const bool xcd8 = [] {
-    const char* e = std::getenv("PHX_GX8");
-    return !(e && e[0] == '0');
-  }();
+  static const bool xcd8 = env_on("PHX_GX8");
   if (xcd8 && p.gy > 1 && p.gx > 8) p.gx = p.gx / 8 * 8;
   p.P = p.gx;
   p.res_lds = 0;
   // A-resident sweeps (k_gemm2r): a workgroup keeps its M tile of A' in LDS for a run of N tiles, so
   // the A view is applied once per run instead of once per N tile.  Runs are as long as the grid
   // stays >= ~512 workgroups allows; at least 2 N tiles per run, K of at least 2 chunks, no split-K.
-  static const bool res_on = [] {
-    const char* e = std::getenv("PHX_GEMM_RES");
-    return !(e && e[0] == '0');
-  }();
+  static const bool res_on = env_on("PHX_GEMM_RES");
   const bool res_tile = (c.wm == 2 && c.tm == 2 && c.tn == 2) || (c.wm == 4 && c.tm == 1 && (c.tn == 3 || c.tn == 5)) ||
                         (c.wm == 2 && c.tm == 1 && c.tn == 2);
   const int ksteps = (K + bk - 1) / bk;

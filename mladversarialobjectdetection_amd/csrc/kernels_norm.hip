@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 
 namespace phx {
@@ -33,10 +34,7 @@ struct RedPlan {
 // 4 (measured: 8 helps the BN-backward reductions by 14 %, is neutral for the SE pools and slows
 // the SE backward apply)
 static long red_target_blocks() {
-  static long v = [] {
-    const char* e = std::getenv("PHX_RED_BLOCKS");
-    return e ? atol(e) : 1024L;
-  }();
+  static long v = env_long("PHX_RED_BLOCKS", 1024L);
   return v;
 }
 static int red_depth() {

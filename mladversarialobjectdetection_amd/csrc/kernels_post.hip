@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 #include "post.hpp"
 
@@ -282,8 +283,7 @@ static NmsPlan nms_plan(int N) {
   const int fast = std::max(p.lp * 8, kNmsHistBins * 4) + p.lp * 4 + p.lp * 16 + kNmsSelBytes;
   // PHX_NMS_FAST=0: the general queue only (A/B and diagnosis; read per call, so one process can
   // compare both paths bit for bit)
-  const char* fe = std::getenv("PHX_NMS_FAST");
-  const bool fast_on = !(fe && fe[0] == '0');
+  const bool fast_on = env_on("PHX_NMS_FAST");
   p.qrows = fast_on ? std::max(0, std::min(64, (kNmsLdsBytes - fixed - p.ck_bytes - fast) / kNmsRowBytes)) : 0;
   p.lds = std::max(p.lds, fixed + p.ck_bytes + fast + p.qrows * kNmsRowBytes);
   p.lds = (p.lds + 15) / 16 * 16;
@@ -1016,10 +1016,7 @@ size_t soft_nms_work_floats(int B, int N) { return (size_t)B * N * 7; }
 
 // PHX_NMS_STATS=1: each image's soft-NMS reports its candidate count, list size, pops and path
 static int nms_debug() {
-  static const int v = [] {
-    const char* e = std::getenv("PHX_NMS_STATS");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
+  static const int v = env_flag("PHX_NMS_STATS") ? 1 : 0;
   return v;
 }
 

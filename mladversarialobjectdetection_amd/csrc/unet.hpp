@@ -1,5 +1,5 @@
 // unet.hpp — launchers of the defender step (kernels_unet.hip) and the victim-side helper the
-// defender's first pass uses (api.cpp).
+// defender's first pass uses (api.cpp, api_data.cpp, exec.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -78,7 +78,7 @@ void def_perm_crops(const float* images, int* info, float* crops, int B, int H, 
 void def_filter(const float* nb, const float* ns, const int* nc, int B, int maxo, float H, float W, float thresh,
                 float* ob, int* oc, hipStream_t st, float* os = nullptr);
 
-// ---- victim side (api.cpp) -----------------------------------------------------------------
+// ---- victim side (api.cpp; the profiler hooks exec.cpp, the serving preprocess api_data.cpp) -----
 // odet_model (attack_detection.py:96-127): frozen-BN forward, person anchors, soft-NMS, clip and
 // filter_valid_boxes; boxes [B][100][4], count [B]
 // train: the call's training flag (drop connect), pass: drop-connect key (0 first, 1 second);

@@ -1,6 +1,6 @@
 """Inference-BN statistics reuse (GPU): a frozen pass (test_step, bn=frozen, the defender's
 protege) keeps the BN statistics it derived from the moving averages in the executor's slots and
-reuses them while the weights version is unchanged (api.cpp Exec::frozen_ver); a load or a training
+reuses them while the weights version is unchanged (ctx.hpp Exec::frozen_ver); a load or a training
 pass bumps the version.  Checked against PHX_FROZEN_REUSE=0 (every pass recomputes), bit for bit:
 eval steps before and after training steps (the moving statistics move in between), and defender
 steps (the frozen protege's first pass every step)."""
