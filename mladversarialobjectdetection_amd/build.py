@@ -16,7 +16,7 @@ def build(jobs: int = 8, verbose: bool = False) -> str:
     if r.returncode != 0:
         raise RuntimeError("libphx build failed")
     # the kernel parity checkers link against the library (tests/test_gpu_gemm_kernels.py,
-    # tests/test_gpu_conv_kernels.py and tests/test_gpu_norm_kernels.py run them)
+    # tests/test_gpu_conv_kernels.py, tests/test_gpu_norm_kernels.py and tests/test_gpu_conv3_kernels.py run them)
     kern = os.path.join(os.path.dirname(HERE), "tests", "kernels")
     if os.path.isfile(os.path.join(kern, "Makefile")):
         r = subprocess.run(["make", "-C", kern, f"-j{min(jobs, 16)}"], env=env, stdout=subprocess.PIPE,

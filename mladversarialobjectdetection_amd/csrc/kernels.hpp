@@ -42,8 +42,10 @@ int launch_stem_fwd(const float* x, const float* w, float* y, int B, int H, int 
 // dx [B,H,W,3] (+)= conv_transpose(dy); dy is a materialised gradient [B,Ho,Wo,Co]
 void launch_stem_bwd(const float* dy, const float* w, float* dx, int B, int H, int W, int Ho,
                      int Wo, int Co, int pt, int pl, bool acc, hipStream_t s);
-// dx [B,H,W,3] = conv_transpose(gx(dy)) through the stem BN's gradient view, only at pixels some
-// paste owns (owner [B,H,W,3] >= 0; nullptr = everywhere), zero elsewhere; overwrites dx
+// dx [B,H,W,3] = conv_transpose(gx(dy)) through the stem BN's gradient view, per 32 x 32-pixel tile
+// (16 x 16 quads of 2 x 2 pixels, from the image's top left): a tile holding any owned element
+// (owner [B,H,W,3] >= 0; nullptr = everything owned) gets the full data gradient at every in-range
+// pixel, owned or not; a tile with none is written +0.0 everywhere and reads no dy or y.  Overwrites dx
 bool stem_bwd_gx_supported(int Co);
 void launch_stem_bwd_gx(GradX g, const float* w, const int16_t* owner, float* dx, int B, int H, int W,
                         int Ho, int Wo, int Co, int pt, int pl, hipStream_t s);
@@ -200,7 +202,21 @@ struct SepTileInfo {
   int tw, th, tiles_x, ntiles;
 };
 SepTileInfo sep_tile_info(int H, int W);
-void launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s);
+// The stem launchers' plans: k_stem_fwd's 256-pixel blocks (last_valid: the pixels of the last one) and
+// k_stem_bwd_gx's 16 x 16-quad tiles (last_qx / last_qy: the quad columns / rows of the last tile)
+struct StemPlanInfo {
+  int blocks, last_valid, tiles_x, tiles_y, last_qx, last_qy;
+};
+StemPlanInfo stem_plan_info(int B, int H, int W);
+// un_conv3_small's plan for M output rows (kernels_unet.hip): G workgroups of four waves over `tiles`
+// 16-row tiles; xr: the XCD-aware ranges are on, XCD x sweeps xcd_tiles[x] of them (tper each but the
+// last ones) with xcd_wgs[x] workgroups; sweeps: the most tiles one wave walks
+struct Conv3PlanInfo {
+  int G, xr, sweeps;
+  long tiles, tper;
+  int xcd_tiles[8], xcd_wgs[8];
+};
+Conv3PlanInfo conv3_small_plan_info(long M);
 
 // ---- normalisation / elementwise (kernels_norm.hip) ---------------------------------------
 // Per-channel batch statistics of y [M,C]: writes mean/rstd (float) and updates moving stats

@@ -386,6 +386,18 @@ void launch_stem_bwd(const float* dy, const float* w, float* dx, int B, int H, i
   PHX_LAUNCH_CHECK();
 }
 
+StemPlanInfo stem_plan_info(int B, int H, int W) {
+  StemPlanInfo p;
+  const long total = (long)B * (H / 2) * (W / 2);
+  p.blocks = cdiv(total, 256);
+  p.last_valid = (int)(total - (long)(p.blocks - 1) * 256);
+  p.tiles_x = cdiv(W / 2, kStemTQ);
+  p.tiles_y = cdiv(H / 2, kStemTQ);
+  p.last_qx = W / 2 - (p.tiles_x - 1) * kStemTQ;
+  p.last_qy = H / 2 - (p.tiles_y - 1) * kStemTQ;
+  return p;
+}
+
 // ------------------------------------------------------------------------------------------
 // fp32 MFMA GEMM: C[M,N] (+)= A'[M,K] * Bt[N,K]^T + bias, A' = A as seen through an InX view
 // (BN + activation applied on load) optionally scaled per (image, k) (SE excitation).
@@ -1198,20 +1210,6 @@ int launch_gemm_dgrad(GradX A, const float* Bt, float* C, int M, int N, int K, b
     return gemm2_run(A.y ? 3 : 0, raw, A, Bt, nullptr, C, M, N, K, acc, nullptr, 1, s, partial, StatSink{},
                      gemm2_target_wgs(), gs, bf16);
   return gemm1_run(A.y ? 3 : 0, raw, A, Bt, nullptr, C, M, N, K, acc, nullptr, 1, s, partial, StatSink{}, gs);
-}
-
-__global__ void k_transpose(const float* __restrict__ in, float* __restrict__ out, int rows,
-                            int cols) {
-  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)rows * cols) return;
-  int r = (int)(idx / cols), c = (int)(idx % cols);
-  out[(long)c * rows + r] = in[idx];
-}
-
-void launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s) {
-  long n = (long)rows * cols;
-  hipLaunchKernelGGL(k_transpose, dim3(cdiv(n, 256)), dim3(256), 0, s, in, out, rows, cols);
-  PHX_LAUNCH_CHECK();
 }
 
 }  // namespace phx

@@ -965,11 +965,31 @@ void un_wprep(const float* w, float* bt, int kind, int ci, int co, int Kp, hipSt
   PHX_LAUNCH_CHECK();
 }
 
+static long conv3_small_grid(long M) {
+  const long tiles = cdiv(M, 16);
+  return std::min<long>(std::max<long>(cdiv(tiles, 4), 1), 2048);
+}
+
+// k_conv3_small's tile ranges, as the kernel derives them from its grid
+Conv3PlanInfo conv3_small_plan_info(long M) {
+  Conv3PlanInfo p{};
+  p.tiles = (M + 15) / 16;
+  p.G = (int)conv3_small_grid(M);
+  p.xr = p.G >= 8 && PHX_UN_XCD_TILES;
+  p.tper = p.xr ? (p.tiles + 7) / 8 : p.tiles;
+  for (int x = 0; x < (p.xr ? 8 : 1); ++x) {
+    const long tbeg = x * p.tper, tend = std::min(p.tiles, tbeg + p.tper);
+    p.xcd_tiles[x] = (int)std::max<long>(0, tend - tbeg);
+    p.xcd_wgs[x] = p.xr ? (p.G - x + 7) / 8 : p.G;
+    p.sweeps = std::max(p.sweeps, (int)cdiv(p.xcd_tiles[x], (long)p.xcd_wgs[x] * 4));
+  }
+  return p;
+}
+
 bool un_conv3_small(const float* x, const float* Bt, const float* bias, float* out, int B, int H, int W, int C,
                     int Ho, int Wo, int N, int Kp, int mode, int s, int pt, int pl, hipStream_t st) {
   if (N > kConvMaxN || Kp > kConvMaxKp || Kp < 9 * C || (Kp & 3)) return false;
-  const long tiles = cdiv((long)B * Ho * Wo, 16);
-  const dim3 grid((unsigned)std::min<long>(std::max<long>(cdiv(tiles, 4), 1), 2048));
+  const dim3 grid((unsigned)conv3_small_grid((long)B * Ho * Wo));
   const bool vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
 #define PHX_CV(NT, MD, V) hipLaunchKernelGGL((k_conv3_small<NT, MD, V>), grid, dim3(256), 0, st, x, Bt, bias, out, B, H, W, C, Ho, Wo, N, Kp, s, pt, pl)
   switch ((N > 16 ? 4 : 0) + (mode ? 2 : 0) + (vec ? 1 : 0)) {
@@ -996,6 +1016,7 @@ static long wgrad_rows_per_slice(long M, int Co, int Kp) {
   return (cdiv(M, ns) + 15) / 16 * 16;
 }
 
+long un_wgrad_rows_per_slice(long M, int Co, int Kp) { return wgrad_rows_per_slice(M, Co, Kp); }
 int un_wgrad_slices(long M, int Co, int Kp) { return (int)cdiv(M, wgrad_rows_per_slice(M, Co, Kp)); }
 
 void un_wgrad(const float* dy, int ldy, const float* x, int ldx, int src, int B, int H, int W, int C, long M,

@@ -29,6 +29,7 @@ void un_wprep(const float* w, float* bt, int kind, int ci, int co, int Kp, hipSt
 // fly from x: src 0 = x itself [M][ldx]; src 1 = 3x3 conv (stride 1, pads 1) over x [B,H,W,C];
 // src 2 = stride-2 transposed conv over x [B,H/2,W/2,C] (rows = the B*H*W outputs)
 int un_wgrad_slices(long M, int Co, int Kp);
+long un_wgrad_rows_per_slice(long M, int Co, int Kp);  // host only, read-only (tests/kernels/conv3_parity)
 void un_wgrad(const float* dy, int ldy, const float* x, int ldx, int src, int B, int H, int W, int C, long M,
               int Co, int Kp, int Kin, int taps, int kind, float* part, float* g, hipStream_t st);
 
