@@ -17,14 +17,17 @@ def build(jobs: int = 8, verbose: bool = False) -> str:
         raise RuntimeError("libphx build failed")
     # the kernel parity checkers link against the library (tests/test_gpu_gemm_kernels.py,
     # tests/test_gpu_conv_kernels.py, tests/test_gpu_norm_kernels.py and tests/test_gpu_conv3_kernels.py run them)
-    kern = os.path.join(os.path.dirname(HERE), "tests", "kernels")
-    if os.path.isfile(os.path.join(kern, "Makefile")):
+    # (tests/kernels_sefold: the checker of the SE backward without its dx tensor, tests/test_gpu_sefold_kernels.py)
+    for sub in ("kernels", "kernels_sefold"):
+        kern = os.path.join(os.path.dirname(HERE), "tests", sub)
+        if not os.path.isfile(os.path.join(kern, "Makefile")):
+            continue
         r = subprocess.run(["make", "-C", kern, f"-j{min(jobs, 16)}"], env=env, stdout=subprocess.PIPE,
                            stderr=subprocess.STDOUT, text=True)
         if verbose or r.returncode != 0:
             sys.stdout.write(r.stdout)
         if r.returncode != 0:
-            raise RuntimeError("tests/kernels build failed")
+            raise RuntimeError(f"tests/{sub} build failed")
     return os.path.join(HERE, "libphx.so")
 
 

@@ -801,6 +801,16 @@ int phx_debug_tap(phx_ctx* ctx, const char* op_name, int which, float* out, size
     if (which == 0 && op.t == OP_DW && E.sep[i])
       throw std::invalid_argument("tap: this depthwise output feeds the fused separable conv's registers only, "
                                   "never stored (PHX_SEP=0 at victim creation keeps it)");
+    if (which == 1 && op.t == OP_BN && i + 1 < E.prog.ops.size() && E.sefold[i + 1]) {
+      // the BN below such an SE: its output's gradient fma(dy, s, dpool / HW) is never stored (the head of
+      // its slot holds dpool); dy, s and dpool are intact after the step
+      const Op& se = E.prog.ops[i + 1];
+      const Tensor& tb = E.prog.tensors[op.out];
+      if (!E.gptr(se.out)) throw std::invalid_argument("tap: no gradient for this tensor");
+      launch_se_da(E.gptr(se.out), E.slot_c[se.slot], E.gptr(op.out), out, tb.n, tb.h * tb.w, tb.c,
+                   (hipStream_t)stream);
+      return PHX_OK;
+    }
     const float* src = which == 0 ? E.tptr(t, nullptr) : E.gptr(op.out);
     if (!src) throw std::invalid_argument("tap: no gradient for this tensor");
     if (which == 0 && E.tbf(t)) launch_bf16_to_f32(src, out, (long)nfloats, (hipStream_t)stream);

@@ -124,6 +124,36 @@ struct StageGradX {
   }
 };
 
+// StageGradX below a squeeze-excite whose input gradient is not stored: g.da is the SE output's
+// gradient, and the BN output's gradient da = fma(d, s[b,c], q[b,c]) (excitation; q = pool gradient
+// * (1 / HW), SeBwdApply's arithmetic bit for bit) is formed here
+template <bool BF>
+struct StageGradXSe {
+  using Raw = typename StageGradX<BF>::Raw;
+  StageGradX<BF> x;
+  float4 s, q;
+  __device__ __forceinline__ void init(const GradX& gx, const float* sp, const float* dp, float inv, int C, int b,
+                                       int c) {
+    x.init(gx, c);
+    s = *reinterpret_cast<const float4*>(sp + (long)b * C + c);
+    const float4 d = *reinterpret_cast<const float4*>(dp + (long)b * C + c);
+    q = make_float4(d.x * inv, d.y * inv, d.z * inv, d.w * inv);
+  }
+  __device__ __forceinline__ Raw zero() const { return x.zero(); }
+  __device__ __forceinline__ Raw load(long e) const { return x.load(e); }
+  __device__ __forceinline__ Raw se(const Raw& r) const {
+    return Raw{make_float4(fmaf(r.d.x, s.x, q.x), fmaf(r.d.y, s.y, q.y), fmaf(r.d.z, s.z, q.z), fmaf(r.d.w, s.w, q.w)),
+               r.y};
+  }
+  __device__ __forceinline__ float4 finish(const Raw& r) const { return x.finish(se(r)); }
+  static constexpr bool kActT = true;
+  __device__ __forceinline__ int act() const { return x.act(); }
+  template <int ACT>
+  __device__ __forceinline__ float4 finish_t(const Raw& r) const {
+    return x.template finish_t<ACT>(se(r));
+  }
+};
+
 __device__ __forceinline__ void fma4(float4& a, const float4& x, const float4& w) {
   a.x = fmaf(x.x, w.x, a.x);
   a.y = fmaf(x.y, w.y, a.y);

@@ -292,6 +292,12 @@ static void ck_bwd(Exec& E, int i, hipStream_t s) {
   const Program& P = E.prog;
   const Op& op = P.ops[i];
   const std::string nm = "b " + std::to_string(i) + " " + op.name;
+  if (op.t == OP_SE && E.sefold[i]) {
+    // its input's gradient is never stored: the head of that slot holds dpool [B][C]
+    const Tensor& ti = P.tensors[op.in[0]];
+    ck_note(E, nm + " dpool", E.gptr(op.in[0]), (size_t)ti.n * ti.c * 4, s);
+    return;
+  }
   if (op.t == OP_BN) {
     const int C = P.tensors[op.in[0]].c;
     ck_note(E, nm + " mdz", E.slot_d[op.slot], C * 4, s);
@@ -868,6 +874,8 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
       ck_bwd(E, i, s);
       continue;
     }
+    const bool se_fold = op.t == OP_SE && E.sefold[i];
+    const bool dw_fold = op.t == OP_DW && i + 2 < (int)P.ops.size() && E.sefold[i + 2];
     const Tensor& ti = P.tensors[op.in[0]];
     const Tensor& to = P.tensors[op.out];
     const float* dy = E.gptr(op.out);
@@ -879,7 +887,7 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
       case OP_PW: kind = "gemm"; fl = 2.0 * ti.rows() * ti.c * to.c; by += 4.0 * ti.c * to.c; break;
       case OP_DW: kind = "dw_bwd"; fl = 2.0 * to.numel() * op.k * op.k; break;
       case OP_BN: kind = "bn_bwd_reduce"; by = 4.0 * 2.0 * ti.numel(); break;
-      case OP_SE: kind = "se_bwd"; by = 4.0 * 3.0 * ti.numel(); break;
+      case OP_SE: kind = "se_bwd"; by = 4.0 * (se_fold ? 2.0 : 3.0) * ti.numel(); break;
       default: break;
     }
     // algorithmic bytes of a dgrad: a gradient view also reads the BN input; accumulation
@@ -924,6 +932,16 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
                                op.acc[0], s, E.gpart, gsk, E.bf16);
         break;
       case OP_DW:
+        if (dw_fold) {
+          // the BN output's gradient is formed on load from the SE output's gradient, s and dpool
+          const Op& se = P.ops[i + 2];
+          const Tensor& tb = P.tensors[se.in[0]];
+          GradX g = gview(ctx, E, op.out, input);
+          g.da = E.gptr(se.out);
+          np = launch_dw_bwd_se(g, E.slot_c[se.slot], E.gptr(se.in[0]), 1.0f / (float)(tb.h * tb.w), W + op.w, dx, ti.n, ti.h, ti.w, ti.c, to.h, to.w, op.k, op.stride, op.pad_t, op.pad_l,
+                                op.acc[0], s, gsk);
+          break;
+        }
         np = launch_dw_bwd(gview(ctx, E, op.out, input), W + op.w, dx, ti.n, ti.h, ti.w, ti.c, to.h, to.w, op.k,
                            op.stride, op.pad_t, op.pad_l, op.acc[0], s, gsk);
         break;
@@ -954,6 +972,12 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
         (void)dx;
         break;
       case OP_SE:
+        if (se_fold) {
+          // dpool goes to the head of the slot of the gradient that is no longer stored
+          np = launch_se_bwd_sums(dy, view(ctx, E, op.in[0], input), ti.n, ti.h * ti.w, ti.c, op.cse, W + op.w1,
+                                  ctx->wt_of(op.w2), op.act, E.slot_b[op.slot], E.slot_c[op.slot], dx, s, E.red, gsk);
+          break;
+        }
         np = launch_se_bwd(dy, view(ctx, E, op.in[0], input), dx, ti.n, ti.h * ti.w, ti.c, op.cse, W + op.w1,
                            W + op.b1, ctx->wt_of(op.w2), W + op.b2, op.act, E.slot_a[op.slot],
                            E.slot_b[op.slot], E.slot_c[op.slot], E.se_g, op.acc[0], s, E.red, gsk);

@@ -1,5 +1,5 @@
 // exec_plan.cpp — the executor's planner (exec_plan.hpp).  The decisions run in a fixed order, each
-// reading the earlier ones: fused statistics, gradient sinks, groups, fold, sep, sepb.
+// reading the earlier ones: fused statistics, gradient sinks, groups, fold, sep, sepb, sefold.
 #include "exec_plan.hpp"
 
 #include <algorithm>
@@ -339,6 +339,25 @@ ExecPlan plan_program(const Program& prog, int B, int tag, int bn_mode, bool bf1
           sp_need = std::max(sp_need, (size_t)np * tm.c);
         }
       }
+    }
+  }
+  // SE backward without the dx tensor: an SE over a batch-statistics BN (bn=local) whose backward sums it
+  // produces (gfused_bn), fed by an ungrouped depthwise conv that runs its own backward launch, with the SE
+  // the only writer of the BN output's gradient: that gradient is formed on load by the depthwise dgrad and
+  // its slot keeps the SE's dpool.  PHX_SEFOLD=0 keeps the apply pass's store (A/B; read per executor).
+  // No other plan field depends on the flag, and every result keeps its bits.
+  E.sefold.assign(P.ops.size(), 0);
+  {
+    const bool on = env_on("PHX_SEFOLD") && bbn && bn_mode == PHX_BN_LOCAL;
+    for (size_t i = 2; on && i < P.ops.size(); ++i) {
+      const Op& se = P.ops[i];
+      const Op& bn = P.ops[i - 1];
+      const Op& dw = P.ops[i - 2];
+      if (se.t != OP_SE || !se.bwd || se.acc[0]) continue;
+      if (bn.t != OP_BN || !bn.bwd || bn.out != se.in[0] || !E.gfused_bn[i - 1] || E.grp_of[i - 1] >= 0) continue;
+      if (dw.t != OP_DW || !dw.bwd || dw.out != bn.in[0] || E.grp_of[i - 2] >= 0 || E.sepb[i - 2]) continue;
+      if (P.tensors[se.in[0]].c % 4 || P.tensors[se.in[0]].goff < 0) continue;
+      E.sefold[i] = 1;
     }
   }
   E.nreg = E.groups.empty() ? 1 : kMaxSeg;

@@ -51,7 +51,12 @@ struct ExecPlan {
   // sepb[i]: the fused sepconv at depthwise op i also runs its backward in one launch (the pointwise
   // data gradient never stored)
   std::vector<char> sepb;
-  std::vector<int> drop_slot;                  // op id -> row of drop_keep (-1)
+  // sefold[i]: SE op i's backward does not store its input's gradient: it only reduces the BN-backward
+  // sums of the BN i - 1 below it, the depthwise op i - 2 forms that gradient on load, and the gradient's
+  // arena slot keeps the SE's dpool [B][C].  Not a dumped field: no other plan
+  // field depends on it.
+  std::vector<char> sefold;
+  std::vector<int> drop_slot;                 // op id -> row of drop_keep (-1)
   std::vector<int> side_off;                   // BN slot -> channel offset in the deferred statistics
   // host tables the allocator uploads
   std::vector<MovEntry> mov;                   // one entry per BN: its moving statistics
@@ -73,7 +78,7 @@ struct ExecPlan {
 };
 
 // Throws std::runtime_error("anchor count mismatch") when the program's levels do not add up to
-// num_anchors (the context's anchor table).  PHX_SEP, PHX_SEP_MINROWS and PHX_SEPB are read at every
+// num_anchors (the context's anchor table).  PHX_SEP, PHX_SEP_MINROWS, PHX_SEPB and PHX_SEFOLD are read at every
 // call, PHX_FOLD and PHX_GROUP once per process.
 ExecPlan plan_exec(const ModelConfig& mc, int B, int tag, int bn_mode, bool bf16, int num_anchors);
 

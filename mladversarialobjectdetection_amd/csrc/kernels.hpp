@@ -138,6 +138,12 @@ int launch_dw_bwd(GradX dy, const float* w, float* dx, int B, int H, int W, int 
                   int Wo, int k, int stride, int pt, int pl, bool acc, hipStream_t s,
                   GradSink gs = GradSink{});
 int dw_bwd_partials(int B, int H, int W, int C, int Ho, int Wo, int k, int stride, int pt, int pl);
+// launch_dw_bwd below an SE whose input gradient is not stored (launch_se_bwd_sums): dy.da is the SE
+// output's gradient and the kernel stages fma(dy.da, se_s[b,c], se_dpool[b,c] * se_inv), what
+// launch_se_bwd would have stored, in front of the BN backward of the view (dy.y != nullptr)
+int launch_dw_bwd_se(GradX dy, const float* se_s, const float* se_dpool, float se_inv, const float* w, float* dx,
+                     int B, int H, int W, int C, int Ho, int Wo, int k, int stride, int pt, int pl, bool acc,
+                     hipStream_t s, GradSink gs = GradSink{});
 // grouped depthwise convs (same taps w, C, k, stride; per-member tensors and sinks); H, W are the
 // conv input, Ho, Wo its output; out = y (forward) or dx (backward); nps[i] = partial rows
 struct DwSeg {
@@ -292,6 +298,17 @@ int launch_se_bwd(const float* dy, InX x, float* dx, int B, int HW, int C, int C
                   const float* w1, const float* b1, const float* w2t, const float* b2, int act,
                   const float* pool, const float* hidden, const float* scale, float* gsum,
                   bool acc, hipStream_t s, double* scratch, GradSink gs = GradSink{});
+// launch_se_bwd without the dx tensor: the pool reduction and the MLP backward as there (dpool [B*C],
+// 16-B aligned, is the caller's: it must outlive the depthwise dgrad), then the BN-backward sums of
+// da = fma(dy, scale[b,c], dpool[b,c] * (1 / HW)) into gs (required), in launch_se_bwd's arithmetic and
+// order: the partials are bit-equal to the ones launch_se_bwd writes, and da itself is never stored:
+// launch_dw_bwd_se forms it on load.  Returns the partial rows written.
+int launch_se_bwd_sums(const float* dy, InX x, int B, int HW, int C, int Cse, const float* w1, const float* w2t,
+                       int act, const float* hidden, const float* scale, float* dpool, hipStream_t s,
+                       double* scratch, GradSink gs);
+// out [B,HW,C] = fma(dy, scale[b,c], dpool[b,c] * (1 / HW)) (that gradient, materialised for a tap)
+void launch_se_da(const float* dy, const float* scale, const float* dpool, float* out, int B, int HW, int C,
+                  hipStream_t s);
 int ew_gstats_partials(long seg_rows, int C, int nseg);
 // mdz = mean(dz), mdzx = mean(dz*xhat) from the P GradSink partials
 void launch_bn_bwd_finalize(const float2* part, int P, long M, int C, float* mdz, float* mdzx,

@@ -65,6 +65,11 @@ struct DwBwdSeg {
   DwGeom g;
   int acc;
   GradSink gs;
+  // below a squeeze-excite whose input gradient is not stored (k_dw_bwd<..., SE = true>): excitation
+  // and pool gradient [B][C], 1 / HW
+  const float* se_s = nullptr;
+  const float* se_d = nullptr;
+  float se_inv = 0.f;
 };
 template <int NS>
 struct DwBwdGroup {
@@ -320,7 +325,8 @@ __device__ __forceinline__ void dw_gsums(float4 s1, float4 s2, int lcg, int c, l
 }
 
 // YBF: the BN input y (gradient view, GradSink) in bf16 storage; dy and dx stay fp32
-template <int K, int S, int RPT, bool GS, int NS, int SU = 4, bool YBF = false>
+// SE: the gradient view's da is formed on load from a squeeze-excite's output gradient (StageGradXSe)
+template <int K, int S, int RPT, bool GS, int NS, int SU = 4, bool YBF = false, bool SE = false>
 __global__ __launch_bounds__(256) void k_dw_bwd(DwBwdGroup<NS> grp) {
   const DwBwdSeg sg = pick_seg(grp.s, NS == 1 ? 0 : (int)blockIdx.y);
   const GradX& gv = sg.gv;
@@ -344,12 +350,14 @@ __global__ __launch_bounds__(256) void k_dw_bwd(DwBwdGroup<NS> grp) {
   const int oy_lo = S == 1 ? ay : (ay >= 0 ? ay / S : -((-ay + S - 1) / S));
   const int ox_lo = S == 1 ? ax : (ax >= 0 ? ax / S : -((-ax + S - 1) / S));
 
-  StageGradX<YBF> src;
-  src.init(gv, c);
+  using Stage = std::conditional_t<SE, StageGradXSe<YBF>, StageGradX<YBF>>;
+  Stage src;
+  if constexpr (SE) src.init(gv, sg.se_s, sg.se_d, sg.se_inv, g.C, b, c);
+  else src.init(gv, c);
   float4* wt = tile + g.rin * g.cin * CG;
   Taps<K> wr;
   wr.stage(wt, w, g.C, cgi, g.lcg);
-  dw_stage<StageGradX<YBF>, SU>(tile, src, b, g.Ho, g.Wo, g.C, oy_lo, ox_lo, c, g);
+  dw_stage<Stage, SU>(tile, src, b, g.Ho, g.Wo, g.C, oy_lo, ox_lo, c, g);
   __syncthreads();
 
   const int ix = ix0 + col;
@@ -597,7 +605,7 @@ void launch_dw_fwd_group(const DwSeg* segs, int n, int B, int C, const float* w,
   dw_fwd_dispatch(grp, n, B, stats, k, stride, s);
 }
 
-template <int K, int S, int NS>
+template <int K, int S, int NS, bool SE = false>
 static void dw_bwd_go(const DwBwdGroup<NS>& grp, int n, int B, bool gsums, hipStream_t s) {
   int gx = 1;
   size_t lds = 0;
@@ -610,26 +618,26 @@ static void dw_bwd_go(const DwBwdGroup<NS>& grp, int n, int B, bool gsums, hipSt
   const bool ybf = (grp.s[0].gv.y && grp.s[0].gv.ybf) || (gsums && grp.s[0].gs.ybf);
   if (ybf) {
     if (gsums)
-      hipLaunchKernelGGL((k_dw_bwd<K, S, 4, true, NS, 4, true>), grid, dim3(256), lds, s, grp);
+      hipLaunchKernelGGL((k_dw_bwd<K, S, 4, true, NS, 4, true, SE>), grid, dim3(256), lds, s, grp);
     else
-      hipLaunchKernelGGL((k_dw_bwd<K, S, 4, false, NS, 4, true>), grid, dim3(256), lds, s, grp);
+      hipLaunchKernelGGL((k_dw_bwd<K, S, 4, false, NS, 4, true, SE>), grid, dim3(256), lds, s, grp);
     return;
   }
   if (gsums)
-    hipLaunchKernelGGL((k_dw_bwd<K, S, 4, true, NS>), grid, dim3(256), lds, s, grp);
+    hipLaunchKernelGGL((k_dw_bwd<K, S, 4, true, NS, 4, false, SE>), grid, dim3(256), lds, s, grp);
   else
-    hipLaunchKernelGGL((k_dw_bwd<K, S, 4, false, NS>), grid, dim3(256), lds, s, grp);
+    hipLaunchKernelGGL((k_dw_bwd<K, S, 4, false, NS, 4, false, SE>), grid, dim3(256), lds, s, grp);
 }
 
-template <int NS>
+template <int NS, bool SE = false>
 static void dw_bwd_dispatch(const DwBwdGroup<NS>& grp, int n, int B, bool gsums, int k, int stride,
                             hipStream_t s) {
   for (int i = 0; i < n; ++i)
     if (dw_lds(grp.s[i].g, k) > 160 * 1024) throw std::runtime_error("dw: LDS window too large");
-  if (k == 3 && stride == 1) dw_bwd_go<3, 1, NS>(grp, n, B, gsums, s);
-  else if (k == 3 && stride == 2) dw_bwd_go<3, 2, NS>(grp, n, B, gsums, s);
-  else if (k == 5 && stride == 1) dw_bwd_go<5, 1, NS>(grp, n, B, gsums, s);
-  else if (k == 5 && stride == 2) dw_bwd_go<5, 2, NS>(grp, n, B, gsums, s);
+  if (k == 3 && stride == 1) dw_bwd_go<3, 1, NS, SE>(grp, n, B, gsums, s);
+  else if (k == 3 && stride == 2) dw_bwd_go<3, 2, NS, SE>(grp, n, B, gsums, s);
+  else if (k == 5 && stride == 1) dw_bwd_go<5, 1, NS, SE>(grp, n, B, gsums, s);
+  else if (k == 5 && stride == 2) dw_bwd_go<5, 2, NS, SE>(grp, n, B, gsums, s);
   else throw std::invalid_argument("dw: unsupported kernel/stride");
   PHX_LAUNCH_CHECK();
 }
@@ -647,6 +655,21 @@ int launch_dw_bwd(GradX dy, const float* w, float* dx, int B, int H, int W, int 
   grp.s[0] = DwBwdSeg{dy, dx, dw_plan(H, W, C, Ho, Wo, pt, pl, k, stride, 4, true), acc ? 1 : 0, gs};
   grp.s[0].gs.P = B * grp.s[0].g.ntiles;
   dw_bwd_dispatch(grp, 1, B, gs.part != nullptr, k, stride, s);
+  return B * grp.s[0].g.ntiles;
+}
+
+int launch_dw_bwd_se(GradX dy, const float* se_s, const float* se_dpool, float se_inv, const float* w, float* dx,
+                     int B, int H, int W, int C, int Ho, int Wo, int k, int stride, int pt, int pl, bool acc,
+                     hipStream_t s, GradSink gs) {
+  if (C % 4) throw std::runtime_error("dw: C % 4 != 0");
+  if (!dy.y || !se_s || !se_dpool) throw std::runtime_error("dw bwd se: needs a BN gradient view, s and dpool");
+  if ((reinterpret_cast<uintptr_t>(se_s) | reinterpret_cast<uintptr_t>(se_dpool)) & 15)
+    throw std::runtime_error("dw bwd se: unaligned s / dpool");
+  DwBwdGroup<1> grp{};
+  grp.w = w;
+  grp.s[0] = DwBwdSeg{dy, dx, dw_plan(H, W, C, Ho, Wo, pt, pl, k, stride, 4, true), acc ? 1 : 0, gs, se_s, se_dpool, se_inv};
+  grp.s[0].gs.P = B * grp.s[0].g.ntiles;
+  dw_bwd_dispatch<1, true>(grp, 1, B, gs.part != nullptr, k, stride, s);
   return B * grp.s[0].g.ntiles;
 }
 

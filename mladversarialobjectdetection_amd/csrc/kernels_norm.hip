@@ -1058,6 +1058,68 @@ int launch_se_bwd(const float* dy, InX x, float* dx, int B, int HW, int C, int C
   return ew_gstats(SeBwdApply{dy, scale, gsum, dx, C, acc ? 1 : 0, 1.0f / (float)HW, {}, {}}, HW, C, B, gs, s);
 }
 
+// ---- SE backward without the dx tensor --------------------------------------------------------
+// The gradient of the SE input, da = fma(dy, s[b,c], q[b,c]) with q = dpool[b,c] * (1 / HW), is a
+// function of dy and per-(image, channel) constants, so nothing has to store it: the depthwise dgrad
+// below forms it on load (StageGradXSe, dw_stage.hpp).  What is left of the apply pass is the
+// reduction of the BN-backward sums over da, in SeBwdApply's arithmetic and k_ew_gstats' order, so
+// the GradSink partials (and with them mdz, mdzx and every gradient downstream) keep their bits.
+struct SeBwdSums {
+  const float* dy;
+  const float* scale;
+  const float* dpool;
+  int C;
+  float inv;
+  float4 sc, dp;
+  using Raw = float4;
+  __device__ void init(int seg, int c4) {
+    sc = *reinterpret_cast<const float4*>(scale + (long)seg * C + c4 * 4);
+    const float4 d = *reinterpret_cast<const float4*>(dpool + (long)seg * C + c4 * 4);
+    dp = make_float4(d.x * inv, d.y * inv, d.z * inv, d.w * inv);
+  }
+  __device__ Raw load(long m, int c4) const { return *reinterpret_cast<const float4*>(dy + m * C + c4 * 4); }
+  __device__ float4 out(const Raw& g, long, int) const {
+    return make_float4(fmaf(g.x, sc.x, dp.x), fmaf(g.y, sc.y, dp.y), fmaf(g.z, sc.z, dp.z), fmaf(g.w, sc.w, dp.w));
+  }
+};
+
+int launch_se_bwd_sums(const float* dy, InX x, int B, int HW, int C, int Cse, const float* w1, const float* w2t,
+                       int act, const float* hidden, const float* scale, float* dpool, hipStream_t s,
+                       double* scratch, GradSink gs) {
+  if (Cse < 1 || Cse > kSeT) throw std::runtime_error("se: squeeze width outside 1..256");
+  if (!gs.part) throw std::runtime_error("se bwd sums: no GradSink (nothing else is produced)");
+  if (reinterpret_cast<uintptr_t>(dpool) & 15) throw std::runtime_error("se bwd sums: unaligned dpool");
+  const int chunks = x.bf ? colred_parts(SumAcc<true>{x, dy, C, {}}, HW, C, B, scratch, s)
+                          : colred_parts(SumAcc<false>{x, dy, C, {}}, HW, C, B, scratch, s);
+  se_mlp<1>(scratch, chunks, B, C, Cse, 1.f, w2t, nullptr, w1, nullptr, act, scale, nullptr,
+            const_cast<float*>(hidden), dpool, s);
+  return ew_gstats(SeBwdSums{dy, scale, dpool, C, 1.0f / (float)HW, {}, {}}, HW, C, B, gs, s);
+}
+
+// out = fma(dy, s[b,c], dpool[b,c] * inv): the gradient of such an SE's input, for a tap
+__global__ __launch_bounds__(256) void k_se_da(const float4* __restrict__ dy, const float* __restrict__ scale,
+                                               const float* __restrict__ dpool, float inv, float4* __restrict__ out,
+                                               long n4, long per_img, int C) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const long e = i * 4;
+  const long bc = (e / per_img) * C + e % C;
+  const float4 g = dy[i];
+  const float4 sc = *reinterpret_cast<const float4*>(scale + bc);
+  const float4 d = *reinterpret_cast<const float4*>(dpool + bc);
+  out[i] = make_float4(fmaf(g.x, sc.x, d.x * inv), fmaf(g.y, sc.y, d.y * inv), fmaf(g.z, sc.z, d.z * inv),
+                       fmaf(g.w, sc.w, d.w * inv));
+}
+
+void launch_se_da(const float* dy, const float* scale, const float* dpool, float* out, int B, int HW, int C,
+                  hipStream_t s) {
+  if (C % 4) throw std::runtime_error("se da: C % 4 != 0");
+  const long n4 = (long)B * HW * C / 4;
+  hipLaunchKernelGGL(k_se_da, dim3(cdiv(n4, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(dy), scale, dpool,
+                     1.0f / (float)HW, reinterpret_cast<float4*>(out), n4, (long)HW * C, C);
+  PHX_LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------------------------------
 // elementwise
 // ------------------------------------------------------------------------------------------
