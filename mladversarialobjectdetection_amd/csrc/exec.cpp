@@ -97,10 +97,7 @@ void alloc_exec(Exec& E, int A) {
   const int S = E.ed.H;
   const long nslot = (long)B * PHX_MAX_OUT;
   E.img = E.alloc<ImgParams>(B);
-  {
-    size_t bytes = nslot * sizeof(BoxPlace) + (4 + 2 * B + 3 * nslot + 2 + 8 * B + 8 * nslot) * sizeof(int);
-    E.place = reinterpret_cast<BoxPlace*>(E.alloc<char>(bytes));
-  }
+  E.place = reinterpret_cast<BoxPlace*>(E.alloc<char>(eot_place_bytes(B, PHX_MAX_OUT)));
   E.spans = E.alloc<SpanEntry>(nslot * S);
   E.ysum = E.alloc<double>((size_t)B * 2 * 64);
   E.ymean = E.alloc<float>((size_t)B * 2);

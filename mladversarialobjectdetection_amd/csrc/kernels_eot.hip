@@ -231,11 +231,11 @@ __global__ __launch_bounds__(kBandMaxBoxes) void k_eot_bands(EotDims d, const Bo
   int* bvpre = bcnt + 8 * d.B;                          // [8][B*maxb]
   __shared__ int sc[8][kBandMaxBoxes];
   const int b = blockIdx.x, j = threadIdx.x, n = img_n[b], v = img_first[b] + j;
-  const int nt = j < n ? (place[vlist[v]].ps + kResizeRT - 1) / kResizeRT : 0;
+  const int ps = j < n ? place[vlist[v]].ps : 0;  // (ps 0: no tiles)
   int c[8];
 #pragma unroll
   for (int x = 0; x < 8; ++x) {
-    c[x] = (x + 1) * nt / 8 - x * nt / 8;
+    c[x] = EotPlanInfo::band_tiles(ps, x, kResizeRT);
     sc[x][j] = c[x];
   }
   __syncthreads();
@@ -258,13 +258,14 @@ __global__ __launch_bounds__(kBandMaxBoxes) void k_eot_bands(EotDims d, const Bo
 void launch_eot_place(const EotDims& d, const float* boxes, const int* count, const float* params,
                       uint64_t seed, int64_t step, int gimg0, ImgParams* img, BoxPlace* place,
                       SpanEntry* spans, int* err, hipStream_t s, PlaceRule rule) {
+  // refused before anything is launched: the outputs stay as they were
+  if (d.maxb > kBandMaxBoxes) throw std::invalid_argument("eot: more than 128 box slots per image");
   int* lists = reinterpret_cast<int*>(place + (long)d.B * d.maxb);
   hipLaunchKernelGGL(k_eot_place, dim3(1), dim3(256), 0, s, d, boxes, count, params, seed, step,
                      gimg0, img, place, lists, err, rule);
   PHX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_eot_spans, dim3(2, d.B * d.maxb), dim3(256), 0, s, d, place, spans);
   PHX_LAUNCH_CHECK();
-  if (d.maxb > kBandMaxBoxes) throw std::invalid_argument("eot: more than 128 box slots per image");
   hipLaunchKernelGGL(k_eot_bands, dim3(d.B), dim3(kBandMaxBoxes), 0, s, d, place);
   PHX_LAUNCH_CHECK();
 }
@@ -684,8 +685,7 @@ __global__ __launch_bounds__(256) void k_eot_resize(EotDims d, const float* __re
     const int sl = L.vlist[v];
     const BoxPlace P = place[sl];
     const int k = sl % d.maxb;
-    const int nt = (P.ps + kResizeRT - 1) / kResizeRT;
-    const int i0 = (xb * nt / 8 + (local - bv[v])) * kResizeRT;
+    const int i0 = (EotPlanInfo::band_first(P.ps, xb, kResizeRT) + (local - bv[v])) * kResizeRT;
     const int ni = min(kResizeRT, P.ps - i0);
     const SpanEntry* sp = spans + (long)sl * d.span_stride;
     const float scale = (float)P.ps / (float)d.P;
@@ -994,6 +994,8 @@ void launch_eot_composite(const EotDims& d, const float* img_in, const BoxPlace*
                        img_out, owner, mask);
   PHX_LAUNCH_CHECK();
 }
+
+EotPlanInfo eot_plan_info() { return EotPlanInfo{kResizeRT, kResizeGrid, kBoxGrid, kBandMaxBoxes}; }
 
 // ------------------------------------------------------------------------------------------
 // backward

@@ -69,7 +69,34 @@ struct PlaceRule {
   int random_scale = 0;
   float scale_lo = 0.f, scale_hi = 0.f;
 };
+// bytes of the `place` block: B * maxb BoxPlace, then the compact lists k_eot_place and k_eot_bands
+// write behind them (nvalid, total_chunks, img_n [B], img_first [B], vlist [B*maxb], cprefix and
+// tprefix [B*maxb + 1] each, bcnt [8][B], bvpre [8][B*maxb]; two spare ints)
+inline size_t eot_place_bytes(int B, int maxb) {
+  const size_t nslot = (size_t)B * maxb;
+  return nslot * sizeof(BoxPlace) + (4 + 2 * (size_t)B + 3 * nslot + 2 + 8 * (size_t)B + 8 * nslot) * sizeof(int);
+}
+// read-only view of the EOT launch plan's constants (kernels_eot.hip), for the parity harness
+struct EotPlanInfo {
+  int rows_per_tile;    // output rows per resize work item (forward and the adjoint's rows kernel)
+  int resize_grid;      // workgroups of k_eot_resize: workgroup j serves XCD band j % 8
+  int box_grid;         // workgroups of the (box, chunk) and (box, row tile) kernels
+  int band_max_boxes;   // box slots per image k_eot_bands scans (launch_eot_place refuses more)
+  // XCD band x (0..7) of a ps-row box holds row tiles x*nt/8 .. (x+1)*nt/8 - 1 of its nt: the first tile and
+  // the tile count (k_eot_bands and k_eot_resize take both from here)
+  __host__ __device__ static int band_first(int ps, int x, int rows_per_tile) {
+    const int nt = (ps + rows_per_tile - 1) / rows_per_tile;
+    return x * nt / 8;
+  }
+  __host__ __device__ static int band_tiles(int ps, int x, int rows_per_tile) {
+    const int nt = (ps + rows_per_tile - 1) / rows_per_tile;
+    return (x + 1) * nt / 8 - x * nt / 8;
+  }
+};
+EotPlanInfo eot_plan_info();
 // placement + per-image print parameters (+ R offsets).  boxes [B,maxb,4], count [B].
+// Images are square in every caller.  diag is capped by W alone: with H < diag the placement's ymin
+// would go negative and k_eot_rot_bwd would index rows outside the image (H >= W is the contract).
 void launch_eot_place(const EotDims& d, const float* boxes, const int* count, const float* params,
                       uint64_t seed, int64_t step, int gimg0, ImgParams* img, BoxPlace* place,
                       SpanEntry* spans, int* err, hipStream_t s, PlaceRule rule = PlaceRule{});
