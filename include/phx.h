@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PHX_ABI_VERSION 2
+#define PHX_ABI_VERSION 3
 
 #define PHX_PATCH_SIZE 640                               /* attacker.py:43 */
 #define PHX_NPATCH (PHX_PATCH_SIZE * PHX_PATCH_SIZE * 3)
@@ -271,6 +271,53 @@ int phx_eval_step(phx_ctx* ctx, const float* images, int B, const float* boxes,
                   int global_image_offset, int add_tv, float* metrics, float* out_boxes,
                   float* out_scores, int32_t* out_count, void* stream);
 
+/* ---- training summaries (PatchAttacker.vis_images, attacker.py:257-305) -------------------------
+ * What the reference's call hands to TensorBoard every visualize_freq steps, computed on the device.
+ * All three calls work in a context of either compute dtype: what they read — images, the patched
+ * batch, soft-NMS boxes and scores — is fp32 in both.  Arguments are checked on the host before
+ * anything is launched (PHX_EINVAL with a message naming the argument); no call allocates or
+ * synchronises, and no workspace is added (the first phx_set_next reserves two label slots of 2.4 KB
+ * per image of max_batch for the prefetched detections, counted by phx_workspace_bytes from then on).
+ *
+ * phx_vis_sample: the "Sample" image of a batch, the box-drawing sibling of phx_soft_nms:
+ *   images = tf.image.draw_bounding_boxes(images, convert_format(boxes_a), [[0., 1., 0.]])
+ *   images = tf.image.draw_bounding_boxes(images, convert_format(boxes_b), [[0., 0., 1.]])
+ *   tf.cast(tf.clip_by_value(images * stddev_rgb + mean_rgb, 0., 255.), tf.uint8)      (truncating)
+ * in one pass with the model's own constants; every multiply and add rounds on its own.  images
+ * [B,H,W,3] float32; a box set is boxes [B,n,4] pixels (ymin, xmin, ymax, xmax) with count [B] valid
+ * rows (1 <= n <= 511; boxes NULL = no such set); image b is written as H*W*3 bytes at out_u8 +
+ * b * out_stride + out_offset (bytes; out_stride >= H*W*3), so two calls can interleave their images.
+ * The colours are TF float colours written into the normalised image, so drawn pixels come out as
+ * mean_rgb (0) or mean_rgb + stddev_rgb (1) per channel, as the reference's do.
+ * draw_bounding_boxes as restated here ([TF-recall], parity unpinned): convert_format divides in fp32
+ * (ymin / h, xmin / w, ...); the op takes min_row = trunc((ymin / h) * (H - 1)) in fp32, likewise
+ * max_row, min_col, max_col; a box with min > max on an axis or wholly outside the image draws
+ * nothing; otherwise the top line is drawn if min_row >= 0, the bottom if max_row < H, the left if
+ * min_col >= 0, the right if max_col < W, each over the clamped range of the other axis, one pixel
+ * thick.  box.to_tensor() pads every image's list with zero boxes up to the batch's longest count (taken
+ * from `count` on the device), and a zero box paints pixel (0, 0). */
+int phx_vis_sample(phx_ctx* ctx, const float* images, int B, int H, int W, const float* boxes_a,
+                   const int32_t* count_a, int n_a, const float* boxes_b, const int32_t* count_b, int n_b,
+                   uint8_t* out_u8, int64_t out_stride, int64_t out_offset, void* stream);
+/* The counts behind calc_asr (attacker.py:238-255) at T thresholds: out_counts[t] = number of
+ * scores[b][j] >= thresholds[t] over j < count[b] (count NULL: N).  scores [B,N] float32 and out_counts
+ * [T] int32 are device memory; thresholds [T] is a HOST array, 1 <= T <= 128.  Exact integers. */
+int phx_score_curve(phx_ctx* ctx, const float* scores, const int32_t* count, int B, int N, const float* thresholds,
+                    int T, int32_t* out_counts, void* stream);
+/* Both for the last phx_step_grad or phx_eval_step on this context, from what that step left in its
+ * executor: curve_counts int32 [2,T] = the counts of its first-pass detections (row 0: the labels, also
+ * with injected placement boxes, exactly what PHX_M_ASR_DEN counts at 0.5) and of its second-pass
+ * soft-NMS output (row 1: PHX_M_ASR_NUM at 0.5) at thresholds [T] (host); sample_u8 [B,S,S,3] = its
+ * patched batch with the first-pass boxes as set a and the second-pass boxes as set b.  Either output
+ * may be NULL.  A step that placed its patches by a phx_set_next prefetch is read where it read: a
+ * prefetch's detections go to one of two label slots of the context that no other entry point writes,
+ * and the prefetch a step issues itself goes to the other one.  PHX_ESTATE when no step has run, or when its
+ * executor was rebuilt (evicted) or used by another call that runs the victim or pastes patches
+ * (phx_detect, phx_first_pass, phx_patch_images, phx_serve, a defender on this context) since.
+ * The step itself is unchanged: it issues the launches it issued without this call. */
+int phx_step_summary(phx_ctx* ctx, const float* thresholds, int T, int32_t* curve_counts, uint8_t* sample_u8,
+                     void* stream);
+
 /* Keras Adam (ResourceApplyAdam, beta1 .9, beta2 .999, eps 1e-7; attacker_train.py:38) on
  * [patch | scale] followed by the variable constraints clip(patch,-1,1), clip(scale,0,1)
  * (attacker.py:51-54).  m, v: PHX_NPARAM floats each.  t = 1-based iteration. */
@@ -409,6 +456,25 @@ int phx_def_eval_step(phx_def* d, const float* images, int B, const float* boxes
                       const float* params, const float* eval_patch, float* metrics, float* out_boxes,
                       float* out_scores, int32_t* out_count, int64_t step, int32_t global_image_offset,
                       void* stream);
+/* PatchAttackDefender.vis_images (attack_detection.py:239-288) for the last phx_def_step_grad (without
+ * caller boxes) or phx_def_eval_step, from what that step left in the workspace.  "Original" is the
+ * step's first pass (training) or its attacked second pass (evaluation); "recovered" is
+ * odet_model(clip(patched + updates, -1, 1), score_thresh=0.) with the step's own updates, run here with
+ * the victim in inference mode (inference BN, no drop connect, no moving statistic changed).
+ * sample_u8 [2B,S,S,3]: the attacked image b with the original boxes in [0,1,0] at slot 2b, the
+ * recovered image with the recovered boxes in [0,0,1] at slot 2b + 1 (phx_vis_sample's arithmetic).
+ * orig_* / rec_*: boxes [B,100,4], scores [B,100], count [B] (device; rows beyond count are zero).  Any
+ * output may be NULL, not all.  params is not read (the step's updates are): it may be NULL.
+ * Nothing a step computes changes: no variable, no moving statistic, no later gradient.  Waits for a
+ * phx_def_set_next prefetch as phx_def_eval_step does and leaves it valid.  Works over a victim of
+ * either compute dtype (the buffers read and written are fp32).  PHX_ESTATE when no such step has run
+ * since the workspace was built, after a step with caller boxes (they carry no scores) and after a
+ * phx_def_recover (it reuses the step's buffers).  The first call of a workspace reserves the recovered
+ * batch [B,S,S,3] and its detections (synchronous); from then on phx_def_workspace_bytes counts them.
+ * The 3.2 KB per image of detections every step retains for this call are part of the workspace from
+ * its creation and counted from there. */
+int phx_def_summary(phx_def* d, const float* params, uint8_t* sample_u8, float* orig_boxes, float* orig_scores,
+                    int32_t* orig_count, float* rec_boxes, float* rec_scores, int32_t* rec_count, void* stream);
 /* ---- frame recovery (demo_v2.py:151-169 RecoveryDemo.serve, :133-134 run's uint8 cast) ----------
  * The trained U-Net applied to raw frames.  For one uint8 RGB frame [h,w,3] at the victim's image size
  * S with its mean_rgb / stddev_rgb:

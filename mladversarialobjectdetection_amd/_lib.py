@@ -12,7 +12,7 @@ import json
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 PATCH_SIZE = 640
 NPATCH = PATCH_SIZE * PATCH_SIZE * 3
 NPARAM = NPATCH + 1
@@ -94,6 +94,12 @@ _SIGS = [
     ("phx_eval_step", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # training summaries (thresholds is a host array)
+    ("phx_vis_sample", c_int,
+     [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+      c_int64, c_int64, c_void_p]),
+    ("phx_score_curve", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    ("phx_step_summary", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     ("phx_adam_clip", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     ("phx_letterbox", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -128,6 +134,8 @@ _SIGS = [
     ("phx_def_eval_step", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_int64, c_int, c_void_p]),
+    ("phx_def_summary", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # frame recovery (offsets / dims / out_offsets are host arrays)
     ("phx_recover_dims", c_int, [c_int, c_void_p, c_int, c_void_p]),
     ("phx_def_recover", c_int,

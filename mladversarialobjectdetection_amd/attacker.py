@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from . import distributed as ddp
+from . import summaries
 from . import tiff
 from . import weights as wmod
 
@@ -335,7 +336,12 @@ class PatchAttacker:
                "asr_to_scale")
 
     def __init__(self, model: EfficientDetVictim, initial_patch=None, config_override=None,
-                 visualize_freq=200, *, seed=0, learning_rate=1e-2, device=None, matcher="brightness"):
+                 visualize_freq=200, *, seed=0, learning_rate=1e-2, device=None, matcher="brightness",
+                 summary_writer=None):
+        """summary_writer (summaries.py; None = no summaries, and no launch beyond the step's own): when
+        set, train_step hands vis_images() to it at every step with cur_step % visualize_freq == 0 and
+        test_step at every such val step, as the reference's call does (attacker.py:209-213); a
+        visualize_freq of 0 or less means never."""
         if matcher not in MATCHERS:
             raise ValueError("matcher must be 'brightness' (the reference's Patcher) or 'histogram'")
         self.matcher = matcher
@@ -364,6 +370,9 @@ class PatchAttacker:
         self.iterations = 0
         self.cur_step = 0
         self.visualize_freq = visualize_freq
+        self.summary_writer = summary_writer
+        self._val_step = 0  # attacker.py:69, counted by test_step
+        self._last_B = None  # batch size of the last call (vis_images)
         self._patcher = Patcher(self)
         self._matcher = MATCHERS[matcher][1](model)
         self.metrics = {k: _Mean() for k in self.METRICS}
@@ -405,6 +414,7 @@ class PatchAttacker:
         placement (injected boxes).  The metric row of the step is left in metrics_buf."""
         images = self.model._check_images(images)
         B = images.shape[0]
+        self._last_B = B
         if add_tv is None:
             add_tv = ddp.rank() == 0  # TV counted once per global step
         if boxes is not None:
@@ -487,6 +497,45 @@ class PatchAttacker:
         for old in [k for k in self._snapshots if k < ids[-1] - 1024]:
             del self._snapshots[old]
 
+    def vis_images(self, training=True):
+        """PatchAttacker.vis_images (attacker.py:257-305) for the step just run (call() or
+        call(training=False)), as arrays instead of TensorBoard summaries:
+
+        "Patch"   uint8 [640,640,3], training only: clip(patch * stddev_rgb + mean_rgb, 0, 255), the
+                  arithmetic of save_weights' patch.png
+        "ASR"     (bins, asr): calc_asr at every threshold of self.bins, asr = 1 - 4n / (4d + 1e-7) in
+                  float32 (_derive's rule) with d / n the step's first- / second-pass detections >= bin
+        "Sample"  uint8 [B,S,S,3]: the patched batch with the first-pass boxes ([0,1,0]) and the
+                  second-pass boxes ([0,0,1]) drawn, denormalised (phx_step_summary)
+
+        Rank-local, like the reference's (it visualises on one GPU): the counts are this rank's shard's
+        and no collective is issued.  Synchronises with the device."""
+        ctx = self.model.ctx
+        S = ctx.image_size
+        dev = self.params.device
+        bins = np.ascontiguousarray(self.bins, np.float32)
+        if self._last_B is None:
+            raise _lib.PhxError("vis_images: no step has run")
+        B = self._last_B
+        counts = torch.empty(2, len(bins), dtype=torch.int32, device=dev)
+        sample = torch.empty(B, S, S, 3, dtype=torch.uint8, device=dev)
+        ctx.call("phx_step_summary", bins.ctypes.data, len(bins), counts.data_ptr(), sample.data_ptr(), _stream())
+        out = {}
+        if training:
+            patch = self.patch.detach().cpu().numpy()
+            img = np.clip(patch * np.asarray(self.config.stddev_rgb, np.float32)
+                          + np.asarray(self.config.mean_rgb, np.float32), 0, 255)
+            out["Patch"] = img.astype(np.uint8)
+        c = counts.cpu().numpy()
+        asr = (np.float32(1.0) - (np.float32(4.0) * c[1].astype(np.float32))
+               / (np.float32(4.0) * c[0].astype(np.float32) + np.float32(1e-7))).astype(np.float32)
+        out["ASR"] = (bins.copy(), asr)
+        out["Sample"] = sample.cpu().numpy()
+        return out
+
+    def _summarise(self, training, step):
+        summaries.write(self.summary_writer, self.vis_images(training), step, "train" if training else "val")
+
     def train_step(self, inputs, boxes=None, next_inputs=None):
         """attacker.py:307-316: grads = self(inputs); apply_gradients; return metrics.  The metric
         dict is evaluated lazily (like the tensors Keras returns): reading it synchronises.
@@ -506,6 +555,10 @@ class PatchAttacker:
             self.model.ctx.call("phx_set_next", nx.data_ptr(), nx.shape[0], self.global_offset(nx.shape[0]))
         self.call(inputs, boxes=boxes)
         del prev
+        # tf.cond(cur_step % visualize_freq == 0, vis_images) inside call (attacker.py:209-213): before the
+        # update, with the step number the step ran with
+        if summaries.due(self.summary_writer, self.cur_step, self.visualize_freq):
+            self._summarise(True, self.cur_step)
         sid = self._step_id
         self._step_id += 1
         self.allreduce_gradients()
@@ -522,6 +575,9 @@ class PatchAttacker:
         gradient and no update.  Returns (metrics, (boxes_pred, scores_pred, count)) where the
         predictions are call()'s soft-NMS person detections on the patched images."""
         preds = self.call(inputs, training=False, boxes=boxes)
+        if summaries.due(self.summary_writer, self._val_step, self.visualize_freq):
+            self._summarise(False, self._val_step)
+        self._val_step += 1
         ddp.allreduce_sum_(self.metrics_buf)  # every rank, same point: the metric row's one collective
         return self.step_metrics(), preds
 

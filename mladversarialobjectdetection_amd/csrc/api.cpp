@@ -125,10 +125,11 @@ uint64_t phx::ctx_generation(const phx_ctx* ctx) {
 }
 
 void phx::def_first_pass(phx_ctx* ctx, const float* images, int B, int64_t step, int gimg0, float* boxes, int* count,
-                    hipStream_t s, bool train, int pass, float score_thresh, float* scores) {
+                    hipStream_t s, bool train, int pass, float score_thresh, float* scores, DefKeep keep) {
   if (!ctx->weights_loaded) throw std::logic_error("weights not loaded");
   if (B <= 0 || B > ctx->max_batch) throw std::out_of_range("batch exceeds max_batch");
   Exec& E = ctx->exec_for(B);
+  ctx->sum_clobber(E);
   // the protege's layers are frozen (inference BN); the call's training flag still reaches its
   // drop connect (attack_detection.py:46-47, 183)
   run_forward(ctx, E, images, s, pass, step, gimg0, train, true);
@@ -140,7 +141,7 @@ void phx::def_first_pass(phx_ctx* ctx, const float* images, int B, int64_t step,
   run_nms(ctx, E, 4, E.nms1_boxes, E.nms1_scores, E.nms1_count, s, nt);
   const float S = (float)ctx->mc.image_size;
   def_filter(E.nms1_boxes, E.nms1_scores, E.nms1_count, B, PHX_MAX_OUT, S, S, ctx->filter_thresh, boxes, count, s,
-             scores);
+             scores, keep);
 }
 
 // the EOT forward and the staging of caller boxes: the step's, and phx_patch_images' (api_data.cpp)
@@ -293,7 +294,9 @@ int phx_workspace_bytes(phx_ctx* ctx, int B, size_t* bytes) {
   size_t tot = ctx->exec_for(B).bytes;
   for (const auto& e : ctx->execs)  // + the concurrent first pass's executor, once a step made it
     if (e->B == B && e->tag != 0) tot += e->bytes;
-  *bytes = tot + ctx->srv_bytes;  // + the serving frame tables, once a serving call made them
+  // + the serving frame tables, once a serving call made them, and the prefetch's label slots, once a
+  // phx_set_next made them
+  *bytes = tot + ctx->srv_bytes + ctx->pre_lab_bytes;
   return PHX_OK;
   PHX_CATCH(ctx)
 }
@@ -350,6 +353,7 @@ int phx_detect(phx_ctx* ctx, const float* images, int B, float* scores, int32_t*
   check_ready(ctx, B);
   hipStream_t s = (hipStream_t)stream;
   Exec& E = ctx->exec_for(B);
+  ctx->sum_clobber(E);
   run_forward(ctx, E, images, s, 2, 0, 0);
   run_pre_nms(ctx, E, s);
   const long BA = (long)B * ctx->A;
@@ -367,6 +371,7 @@ int phx_first_pass(phx_ctx* ctx, const float* images, int B, float* ob, float* o
   check_ready(ctx, B);
   hipStream_t s = (hipStream_t)stream;
   Exec& E = ctx->exec_for(B);
+  ctx->sum_clobber(E);
   run_forward(ctx, E, images, s, 0, 0, 0);
   run_pre_nms(ctx, E, s, 2);
   run_nms(ctx, E, 2, ob, os, oc, s);
@@ -415,6 +420,15 @@ int phx_set_next(phx_ctx* ctx, const float* next_images, int B, int32_t global_i
     PHX_HIP(hipEventCreateWithFlags(&ctx->ev_pfork, hipEventDisableTiming));
     PHX_HIP(hipEventCreateWithFlags(&ctx->ev_pdone, hipEventDisableTiming));
   }
+  if (next_images && !ctx->pre_lab_mem) {  // the two label slots (ctx.hpp), 2.4 KB per image each
+    // (a slot is a multiple of 256 B, so every array in it keeps 16-B alignment)
+    const size_t mb = (size_t)ctx->max_batch, per = (mb * PHX_MAX_OUT * 5 + mb + 63) / 64 * 64;
+    float* p = dalloc<float>(2 * per);
+    ctx->pre_lab_mem.reset(p);
+    ctx->pre_lab_bytes = 2 * per * sizeof(float);
+    for (int k = 0; k < 2; ++k, p += per)
+      ctx->pre_lab[k] = phx_ctx::Labels{p, p + mb * PHX_MAX_OUT * 4, reinterpret_cast<int*>(p + mb * PHX_MAX_OUT * 5)};
+  }
   ctx->next = next_images ? phx_ctx::Next{next_images, B, global_image_offset} : phx_ctx::Next{};
   // NULL also withdraws a first pass already prefetched for the next step (the caller refilled that
   // batch's buffer in place: the prefetch saw the old contents); the step then runs its own
@@ -440,6 +454,7 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
   hipStream_t s = (hipStream_t)stream;
   Exec& E = ctx->exec_for(B);
   ctx->last = &E;
+  ctx->sum = phx_ctx::Sum{};
   const bool inject = boxes != nullptr;
   // a first pass the previous step prefetched for exactly this batch (phx_set_next)
   const bool use_pre = !inject && ctx->pre.pending && ctx->pre.images == images && ctx->pre.B == B &&
@@ -523,14 +538,19 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
       }
     }
   }
-  Exec* Efp = &E;  // the executor whose first-pass detections place the patches
+  // the first-pass detections that place the patches: this executor's, or a prefetch's label slot
+  phx_ctx::Labels lab{E.nms1_boxes, E.nms1_scores, E.nms1_count};
+  int lab_slot = -1;
   if (!fork && use_pre) {
     // 1'. the prefetched first pass (side executor): its moving-statistics updates, deferred, go in
     // now — after the previous step's second pass, before this step's — and its ASR denominator
-    Efp = &ctx->exec_for(B, 1);
+    // (the pass ran in the side executor; its detections are in a label slot of the context)
+    Exec& Es = ctx->exec_for(B, 1);
     ctx->last = &E;
-    launch_bn_moving_apply(E.mov_tab, E.n_mov, E.mov_cmax, ctx->w(), Efp->side, nullptr, s);
-    launch_count_ge(Efp->nms1_scores, Efp->nms1_count, B, PHX_MAX_OUT, 0.5f, metrics + PHX_M_ASR_DEN, s);
+    lab_slot = ctx->pre.slot;
+    lab = ctx->pre_lab[lab_slot];
+    launch_bn_moving_apply(E.mov_tab, E.n_mov, E.mov_cmax, ctx->w(), Es.side, nullptr, s);
+    launch_count_ge(lab.scores, lab.count, B, PHX_MAX_OUT, 0.5f, metrics + PHX_M_ASR_DEN, s);
   } else if (!fork) {
     // 1. first pass: clean forward, pre_nms, person/valid/threshold filter, soft-NMS
     run_forward(ctx, E, images, s, 0, step, gimg0);
@@ -540,8 +560,8 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
   }
   if (inject && !inject_k) stage_boxes(E, boxes, count, B, maxb, s);  // (unaligned caller boxes)
   // 2. EOT paste
-  eot_forward(ctx, E, images, B, inject ? E.inj_boxes : Efp->nms1_boxes,
-              inject ? E.inj_count : Efp->nms1_count, params, step, gimg0, s);
+  eot_forward(ctx, E, images, B, inject ? E.inj_boxes : lab.boxes, inject ? E.inj_count : lab.count, params, step,
+              gimg0, s);
   launch_eot_count(E.ed, E.place, metrics, s);
   // the next batch's first pass (phx_set_next) on s2 beside this step's second pass and backward:
   // it starts once this step's own first pass and paste are done with the side executor's
@@ -552,6 +572,10 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
   auto prefetch = [&]() {
       Exec& E1 = ctx->exec_for(B, 1);
       ctx->last = &E;
+      // its detections go to the label slot this step did not read, so this step's stay readable after
+      // it (phx_step_summary); no other entry point writes the slots
+      const int slot = lab_slot == 0 ? 1 : 0;
+      const phx_ctx::Labels det = ctx->pre_lab[slot];
       PHX_HIP(hipEventRecord(ctx->ev_pfork, s));
       PHX_HIP(hipStreamWaitEvent(ctx->s2, ctx->ev_pfork, 0));
       struct Defer {
@@ -563,7 +587,7 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
         run_forward(ctx, E1, nx.images, ctx->s2, 0, step + 1, nx.gimg0);
         E1.defer_mov = false;
         run_pre_nms(ctx, E1, ctx->s2, 2);
-        run_nms(ctx, E1, 2, E1.nms1_boxes, E1.nms1_scores, E1.nms1_count, ctx->s2);
+        run_nms(ctx, E1, 2, det.boxes, det.scores, det.count, ctx->s2);
         PHX_HIP(hipEventRecord(ctx->ev_pdone, ctx->s2));
       } catch (...) {
         // a part-way enqueued prefetch: drain it (its side executor is shared with the injected flow's
@@ -572,7 +596,7 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
         ctx->pre = phx_ctx::Pre{};
         throw;
       }
-      ctx->pre = phx_ctx::Pre{nx.images, B, nx.gimg0, step + 1, true};
+      ctx->pre = phx_ctx::Pre{nx.images, B, nx.gimg0, step + 1, true, slot};
   };
   if (!inject && nx.images && nx.B == B && prefetch_ok(ctx, E)) {
     // forked, like the injected flow's concurrent pass, when the second pass reaches the backbone's
@@ -644,6 +668,8 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
     if (fork) ck_post(*E1p, 0, s);
   }
   if (guard_bytes()) check_guards(ctx, s);
+  if (fork) ctx->sum = phx_ctx::Sum{&E, phx_ctx::Labels{E1p->nms1_boxes, E1p->nms1_scores, E1p->nms1_count}, E1p};
+  else ctx->sum = phx_ctx::Sum{&E, lab, lab_slot < 0 ? &E : nullptr};
   return PHX_OK;
   PHX_CATCH(ctx)
 }
@@ -657,6 +683,7 @@ int phx_eval_step(phx_ctx* ctx, const float* images, int B, const float* boxes, 
   hipStream_t s = (hipStream_t)stream;
   Exec& E = ctx->exec_for(B);
   ctx->last = &E;
+  ctx->sum = phx_ctx::Sum{};
   PHX_HIP(hipMemsetAsync(metrics, 0, PHX_NMETRIC * sizeof(float), s));
   run_forward(ctx, E, images, s, 0, step, gimg0, false);
   run_pre_nms(ctx, E, s, 2);
@@ -680,6 +707,7 @@ int phx_eval_step(phx_ctx* ctx, const float* images, int B, const float* boxes, 
   if (out_boxes) PHX_HIP(hipMemcpyAsync(out_boxes, E.nms2_boxes, (size_t)B * PHX_MAX_OUT * 16, hipMemcpyDeviceToDevice, s));
   if (out_scores) PHX_HIP(hipMemcpyAsync(out_scores, E.nms2_scores, (size_t)B * PHX_MAX_OUT * 4, hipMemcpyDeviceToDevice, s));
   if (out_count) PHX_HIP(hipMemcpyAsync(out_count, E.nms2_count, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  ctx->sum = phx_ctx::Sum{&E, phx_ctx::Labels{E.nms1_boxes, E.nms1_scores, E.nms1_count}, &E};
   return PHX_OK;
   PHX_CATCH(ctx)
 }

@@ -167,6 +167,7 @@ int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const in
   // a bn=frozen context's own executor is already planned for inference BN; the others serve from
   // one planned the same way (tag 2), so the result does not depend on bn_mode
   Exec& E = ctx->exec_for(B, ctx->batch_bn() ? 2 : 0);
+  ctx->sum_clobber(E);
   const int S = ctx->mc.image_size;
   if (!E.srv_images) {  // the first serving call of this batch size reserves its buffers
     E.srv_images = E.alloc<float>((size_t)B * S * S * 3);
@@ -382,6 +383,7 @@ int phx_patch_images(phx_ctx* ctx, const float* images, int B, const float* boxe
   hipStream_t s = (hipStream_t)stream;
   Exec& E = ctx->exec_for(B);
   ctx->last = &E;
+  ctx->sum_clobber(E);
   stage_boxes(E, boxes, count, B, maxb, s);
   eot_forward(ctx, E, images, B, E.inj_boxes, E.inj_count, params, step, gimg0, s);
   const int S = ctx->mc.image_size;

@@ -1,4 +1,4 @@
-// ctx.hpp — internal to the library's host side (api.cpp, api_data.cpp, exec.cpp): the context behind
+// ctx.hpp — internal to the library's host side (api.cpp, api_data.cpp, api_vis.cpp, exec.cpp): the context behind
 // the C ABI's phx_ctx, its executors (plan + buffers), the profiler's records and launch-group scope,
 // the error mapping of the C entry points, and the executor's interpreters (exec.cpp).  The defender
 // does not include this: it keeps its narrow window onto the victim (unet.hpp, "victim side").
@@ -27,7 +27,7 @@
 #include "post.hpp"
 #include "unet.hpp"
 
-using namespace phx;  // (only the three host files above include this header)
+using namespace phx;  // (only the host files above include this header)
 
 constexpr float kBnEps = 1e-3f;  // efficientnet_builder.py:179, util_keras.py:35
 
@@ -304,7 +304,35 @@ struct phx_ctx {
     int B = 0, gimg0 = 0;
     int64_t step = -1;
     bool pending = false;
+    int slot = 0;  // which of pre_lab's two label slots holds its detections
   } pre;
+  // A prefetched first pass runs in the side executor, but its soft-NMS output (the labels the consuming
+  // step places its patches by) goes to one of two label slots of the context, which no other entry
+  // point writes: a step that consumes a prefetch issues the next one into the other slot, so its own
+  // labels outlive the step (phx_step_summary), and a validation pass or a defender between a prefetch
+  // and its consumer cannot touch them.  [max_batch,100,4] boxes + [max_batch,100] scores +
+  // [max_batch] counts per slot, reserved by the first phx_set_next and counted by phx_workspace_bytes
+  // from then on.
+  struct Labels {
+    float* boxes = nullptr;
+    float* scores = nullptr;
+    int* count = nullptr;
+  };
+  DPtr pre_lab_mem;
+  Labels pre_lab[2];
+  size_t pre_lab_bytes = 0;
+  // phx_step_summary: the executor of the last phx_step_grad / phx_eval_step (patched batch, second-pass
+  // soft-NMS output) and its first-pass detections where the step read them — a label slot, or the
+  // nms1_* of det_exec; cleared by whatever overwrites that state (another victim call on an executor,
+  // its eviction)
+  struct Sum {
+    Exec* E = nullptr;
+    Labels det;
+    const Exec* det_exec = nullptr;
+  } sum;
+  void sum_clobber(const Exec& e) {
+    if (sum.E == &e || sum.det_exec == &e) sum = Sum{};
+  }
   // `s` waits for a prefetch in flight (it holds the side executor and its deferred statistics)
   void pre_join(hipStream_t s) {
     if (pre.pending) PHX_HIP(hipStreamWaitEvent(s, ev_pdone, 0));

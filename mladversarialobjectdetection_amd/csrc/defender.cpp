@@ -105,6 +105,28 @@ struct phx_def {
   int* pcount[2] = {nullptr, nullptr};
   const float* last_boxes = nullptr;  // the boxes the last step placed its patches by (phx_def_debug)
   const int* last_count = nullptr;
+  // phx_def_summary: the scores of those boxes — the first pass's own (sc) or a prefetch slot's
+  // (pscores) —, the evaluation's attacked second-pass detections (eboxes / escores / ecount), and which
+  // of the two the last step left (sum_kind; 0: neither, e.g. caller boxes, a recovery or a rebuild)
+  float* sc = nullptr;
+  float* pscores[2] = {nullptr, nullptr};
+  const float* last_scores = nullptr;
+  float *eboxes = nullptr, *escores = nullptr;
+  int* ecount = nullptr;
+  enum { SUM_NONE = 0, SUM_TRAIN = 1, SUM_EVAL = 2 };
+  int sum_kind = SUM_NONE;
+  int64_t sum_step = 0;
+  int sum_gimg0 = 0;
+  // the recovered batch clip(patched + updates, -1, 1) and its detections, reserved by the first summary
+  // of a workspace (sum_reserve) and freed with it
+  float *rec = nullptr, *rboxes = nullptr, *rscores = nullptr;
+  int* rcount = nullptr;
+  size_t sum_bytes(int B) const {
+    return ((size_t)B * S * S * 3 + (size_t)B * PHX_MAX_OUT * 5 + (size_t)B) * 4;
+  }
+  void sum_reserve(int B);
+  void summary(uint8_t* sample_u8, float* orig_boxes, float* orig_scores, int* orig_count, float* rec_boxes,
+               float* rec_scores, int* rec_count, hipStream_t s);
   // `s` waits for the prefetch in flight (the victim ctx and its executor are in use until then)
   void join(hipStream_t s) {
     if (pre.pending) PHX_HIP(hipStreamWaitEvent(s, ev_done, 0));
@@ -430,6 +452,18 @@ void phx_def::workspace(int B) {
   }
   last_boxes = boxes;
   last_count = count;
+  // the detections a summary shows (phx_def_summary), 3.2 KB per image: held (and counted) from here
+  // on because a step cannot know whether a summary will follow it
+  sc = alloc<float>((size_t)B * PHX_MAX_OUT);
+  for (int k = 0; k < 2; ++k) pscores[k] = alloc<float>((size_t)B * PHX_MAX_OUT);
+  eboxes = alloc<float>((size_t)B * PHX_MAX_OUT * 4);
+  escores = alloc<float>((size_t)B * PHX_MAX_OUT);
+  ecount = alloc<int>(B);
+  ws_bytes += ((size_t)B * PHX_MAX_OUT * 8 + (size_t)B) * 4;
+  last_scores = nullptr;
+  sum_kind = SUM_NONE;
+  rec = rboxes = rscores = nullptr;
+  rcount = nullptr;
   info = alloc<int>((size_t)B * 3);
   eerr = alloc<int>(1);
   // the evaluation Masker's buffers are reserved by the first evaluation (eval_reserve): a run that
@@ -443,6 +477,14 @@ void phx_def::workspace(int B) {
 // soft-NMS may return 100 overlapping image-sized boxes, so the R store keeps the worst case.
 size_t phx_def::eval_bytes(int B) const {
   return ((size_t)B * PHX_PATCH_SIZE * PHX_PATCH_SIZE * 3 + (size_t)B * PHX_MAX_OUT * S * S * 3) * sizeof(float);
+}
+
+void phx_def::sum_reserve(int B) {
+  if (rec) return;
+  rec = alloc<float>((size_t)B * S * S * 3);
+  rboxes = alloc<float>((size_t)B * PHX_MAX_OUT * 4);
+  rscores = alloc<float>((size_t)B * PHX_MAX_OUT);
+  rcount = alloc<int>(B);
 }
 
 void phx_def::eval_reserve(int B) {
@@ -555,19 +597,23 @@ void phx_def::step(const float* images, int B, const float* boxes_in, const int*
                        pre.gimg0 == gimg0 && pre.gen == ctx_generation(victim);
   join(s);
   pre.pending = false;
+  sum_kind = SUM_NONE;
   prep_weights(W, s);
   // ---- first pass + Masker ----
   const float* bx = boxes_in;
   const int* cn = count_in;
   int used_slot = -1;
+  last_scores = nullptr;  // (caller boxes carry no scores: no summary after such a step)
   if (use_pre) {
     used_slot = pre.slot;
     bx = pboxes[used_slot];
     cn = pcount[used_slot];
+    last_scores = pscores[used_slot];
   } else if (!bx) {
-    def_first_pass(victim, images, B, stp, gimg0, boxes, count, s);
+    def_first_pass(victim, images, B, stp, gimg0, boxes, count, s, true, 0, -1.f, sc);
     bx = boxes;
     cn = count;
+    last_scores = sc;
   }
   last_boxes = bx == boxes_in ? boxes : bx;
   last_count = cn == count_in ? count : cn;
@@ -594,7 +640,8 @@ void phx_def::step(const float* images, int B, const float* boxes_in, const int*
       const int slot = used_slot == 0 ? 1 : 0;
       PHX_HIP(hipEventRecord(ev_fork, s));
       PHX_HIP(hipStreamWaitEvent(side, ev_fork, 0));
-      def_first_pass(victim, next.images, B, stp + 1, next.gimg0, pboxes[slot], pcount[slot], side);
+      def_first_pass(victim, next.images, B, stp + 1, next.gimg0, pboxes[slot], pcount[slot], side, true, 0, -1.f,
+                     pscores[slot]);
       PHX_HIP(hipEventRecord(ev_done, side));
       pre = Pre{next.images, B, next.gimg0, slot, stp + 1, true, ctx_generation(victim)};
     }
@@ -724,6 +771,9 @@ void phx_def::step(const float* images, int B, const float* boxes_in, const int*
     const float* xin = i == 0 ? patched : et[i - 1].p;
     block_bwd(enc[i], xin, H, et[i].y1, et[i].a1, et[i].y2, et[i].denc, tmpT, i == 0 ? nullptr : tmpY);
   }
+  sum_kind = last_scores ? SUM_TRAIN : SUM_NONE;
+  sum_step = stp;
+  sum_gimg0 = gimg0;
 }
 
 // PatchAttackDefender.call(images, training=False) as test_step runs it (attack_detection.py:168-198,
@@ -743,6 +793,7 @@ void phx_def::eval(const float* images, int B, const float* boxes_in, const int*
   e2.rcap = (long)B * PHX_MAX_OUT * S * S * 3;
   eval_reserve(B);
   join(s);  // (a prefetched first pass stays valid: this call only shares the victim executor)
+  sum_kind = SUM_NONE;
   prep_weights(W, s);
   const float* bx = boxes_in;
   const int* cn = count_in;
@@ -757,11 +808,53 @@ void phx_def::eval(const float* images, int B, const float* boxes_in, const int*
   launch_eot_match(e2, eval_patch, img, images, ematched, ysum, ymean, true, s);
   launch_eot_resize(e2, ematched, place, spans, seed, stp, gimg0, erstore, s, 0.1f);
   launch_eot_composite(e2, images, place, erstore, patched, nullptr, s, mask);
-  // the second pass on the patched images (its detections are the evaluation's output)
-  float* ob = out_boxes ? out_boxes : boxes;
-  int* oc = out_count ? out_count : count;
-  def_first_pass(victim, patched, B, stp, gimg0, ob, oc, s, false, 1, 0.f, out_scores);
+  // the second pass on the patched images (its detections are the evaluation's output): kept in the
+  // workspace for a summary and written to the caller's buffers by the same launch
+  DefKeep out;
+  out.boxes = out_boxes ? out_boxes : boxes;
+  out.count = out_count ? out_count : count;
+  out.scores = out_scores;
+  def_first_pass(victim, patched, B, stp, gimg0, eboxes, ecount, s, false, 1, 0.f, escores, out);
   unet_forward(B, W, false, stp, gimg0, metrics, s);
+  sum_kind = SUM_EVAL;
+  sum_step = stp;
+  sum_gimg0 = gimg0;
+}
+
+// PatchAttackDefender.vis_images (attack_detection.py:239-288) for the last step, from what it left in
+// the workspace: `patched` (the images the U-Net read), `upd` (its updates) and the original detections.
+// updated = clip(patched + upd, -1, 1); odet_model(updated, score_thresh=0.) with the victim in inference
+// mode (no drop connect, no moving statistic touched); the attacked image with the original boxes in
+// [0,1,0] at slot 2b and the updated one with the recovered boxes in [0,0,1] at slot 2b + 1.
+void phx_def::summary(uint8_t* sample_u8, float* orig_boxes, float* orig_scores, int* orig_count, float* rec_boxes,
+                      float* rec_scores, int* rec_count, hipStream_t s) {
+  const int B = wsB;
+  const bool ev = sum_kind == SUM_EVAL;
+  const float* ob = ev ? eboxes : last_boxes;
+  const float* os = ev ? escores : last_scores;
+  const int* oc = ev ? ecount : last_count;
+  sum_reserve(B);
+  join(s);  // (a prefetched first pass stays valid: this call only shares the victim executor)
+  const long n = (long)S * S * 3;
+  {
+    DScope g(victim, "def_summary", 0.0, 12.0 * B * n, s);
+    launch_add_clip(patched, upd, rec, (long)B * n, s);
+  }
+  DefKeep out;
+  out.boxes = rec_boxes;
+  out.scores = rec_scores;
+  out.count = rec_count;
+  def_first_pass(victim, rec, B, sum_step, sum_gimg0, rboxes, rcount, s, false, 1, 0.f, rscores, out);
+  if (orig_boxes) PHX_HIP(hipMemcpyAsync(orig_boxes, ob, (size_t)B * PHX_MAX_OUT * 16, hipMemcpyDeviceToDevice, s));
+  if (orig_scores) PHX_HIP(hipMemcpyAsync(orig_scores, os, (size_t)B * PHX_MAX_OUT * 4, hipMemcpyDeviceToDevice, s));
+  if (orig_count) PHX_HIP(hipMemcpyAsync(orig_count, oc, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  if (sample_u8) {
+    float mean[3], stdv[3];
+    ctx_mean_std(victim, mean, stdv);
+    DScope g(victim, "def_summary", 0.0, 2.0 * 5.0 * B * n, s);
+    launch_vis_sample(patched, B, S, S, ob, oc, PHX_MAX_OUT, nullptr, nullptr, 0, mean, stdv, sample_u8, 2 * n, 0, s);
+    launch_vis_sample(rec, B, S, S, nullptr, nullptr, 0, rboxes, rcount, PHX_MAX_OUT, mean, stdv, sample_u8, 2 * n, n, s);
+  }
 }
 
 namespace {
@@ -822,6 +915,7 @@ void phx_def::recover(const uint8_t* src, const std::vector<ServeFrame>& fr, con
   int slot = 0;
   const RecFrame* table = rec_stage(rf, s, &slot);
   join(s);  // (a prefetched first pass stays valid: this call only shares the victim's frame-table ring)
+  sum_kind = SUM_NONE;  // (the canvas replaces the last step's patched batch)
   prep_weights(W, s);
   def_serve_preprocess(victim, src, fr, patched, static_cast<float*>(rec_scales.get()), s);
   unet_forward(B, W, false, 0, 0, nullptr, s);
@@ -929,7 +1023,28 @@ int phx_def_workspace_bytes(phx_def* d, int B, size_t* bytes) {
   if (!d || !bytes || B <= 0 || B > d->max_batch) return PHX_EINVAL;
   DEF_TRY
   d->workspace(B);
-  *bytes = d->ws_bytes;
+  // + the summary's buffers, once a summary reserved them
+  *bytes = d->ws_bytes + (d->rec ? d->sum_bytes(B) : 0);
+  return PHX_OK;
+  DEF_CATCH(d)
+}
+
+int phx_def_summary(phx_def* d, const float* params, uint8_t* sample_u8, float* orig_boxes, float* orig_scores,
+                    int32_t* orig_count, float* rec_boxes, float* rec_scores, int32_t* rec_count, void* stream) {
+  if (!d) return PHX_EINVAL;
+  (void)params;  // the step's own `updates` are read; the variables are not needed again
+  if (!sample_u8 && !orig_boxes && !orig_scores && !orig_count && !rec_boxes && !rec_scores && !rec_count) {
+    d->err = "def_summary: every output (sample_u8, orig_*, rec_*) is null";
+    return PHX_EINVAL;
+  }
+  if (d->sum_kind == phx_def::SUM_NONE || d->wsB == 0 || d->fwdB != d->wsB) {
+    d->err = "def_summary: no phx_def_step_grad (with the victim's first pass) or phx_def_eval_step has run since the "
+             "workspace was built, or a recovery has used it since";
+    return PHX_ESTATE;
+  }
+  DEF_TRY
+  PHX_HIP(hipSetDevice(d->device));
+  d->summary(sample_u8, orig_boxes, orig_scores, orig_count, rec_boxes, rec_scores, rec_count, (hipStream_t)stream);
   return PHX_OK;
   DEF_CATCH(d)
 }

@@ -151,6 +151,7 @@ Exec& phx_ctx::exec_for(int B, int tag) {
     PHX_HIP(hipDeviceSynchronize());
     if (last == execs[lru].get()) last = nullptr;
     if (execs[lru]->tag == 1) pre = Pre{};  // a prefetched first pass lives in the side executor
+    sum_clobber(*execs[lru]);
     execs.erase(execs.begin() + (long)lru);
   }
   auto ex = std::make_unique<Exec>(plan_exec(mc, B, tag, bn_mode, bf16, A));

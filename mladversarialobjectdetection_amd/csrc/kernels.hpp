@@ -463,4 +463,19 @@ void launch_ap_ysum(const uint8_t* img, int B, int H, int W, int out_h, int out_
 void launch_ap_paste(uint8_t* img, int B, int H, int W, const uint8_t* printed, int P, const ApBox* boxes,
                      int max_pix, int slot, const unsigned long long* ysum, const unsigned long long* ysrc, int out_h,
                      int out_w, uint64_t seed, int64_t step, int gimg0, hipStream_t s);
+// ---- training summaries (kernels_vis.hip, attacker.py:257-305, attack_detection.py:239-288) ---
+constexpr int kVisMaxBoxes = 512;  // a box set has fewer slots than this (its staged extents + one padding box)
+constexpr int kCurveMaxT = 128;    // thresholds of one score-curve launch
+// draw_bounding_boxes(set A) then (set B) on images [B,H,W,3], clip(x * std + mean, 0, 255) as uint8:
+// image b goes to out + b * out_stride + out_offset (bytes).  A set is boxes [B,n,4] pixels + count [B]
+// (device); boxes == null: no such set.  mean / stdv: 3 floats (host)
+void launch_vis_sample(const float* images, int B, int H, int W, const float* boxes_a, const int* count_a, int na,
+                       const float* boxes_b, const int* count_b, int nb, const float* mean, const float* stdv,
+                       uint8_t* out, long out_stride, long out_offset, hipStream_t s);
+// out[k][t] = #scores_k[b][j] >= thresholds[t] over j < count_k[b] (count null: N), k = 0 and, if scores1
+// is given, 1; scores [B,N] (device), thresholds [T] (host, T <= kCurveMaxT), out int32 [1 or 2][T] (device)
+void launch_score_curve(const float* scores0, const int* count0, const float* scores1, const int* count1, int B, int N,
+                        const float* thresholds, int T, int* out, hipStream_t s);
+// y = clip(x + u, -1, 1) over n floats
+void launch_add_clip(const float* x, const float* u, float* y, long n, hipStream_t s);
 }  // namespace phx

@@ -923,7 +923,7 @@ __global__ __launch_bounds__(256) void k_def_crops(const float* __restrict__ ima
 // w / W <= 1, h / H <= 1, area > 100 and score >= thresh, in order
 __global__ void k_def_filter(const float* __restrict__ nb, const float* __restrict__ ns, const int* __restrict__ nc,
                              int B, int maxo, float Hf, float Wf, float thresh, float* __restrict__ ob,
-                             int* __restrict__ oc, float* __restrict__ os) {
+                             int* __restrict__ oc, float* __restrict__ os, DefKeep k2) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   int k = 0;
@@ -935,15 +935,26 @@ __global__ void k_def_filter(const float* __restrict__ nb, const float* __restri
       float* o = ob + ((long)b * maxo + k) * 4;
       o[0] = bx[0]; o[1] = bx[1]; o[2] = bx[2]; o[3] = bx[3];
       if (os) os[(long)b * maxo + k] = ns[(long)b * maxo + i];
+      if (k2.boxes) {
+        float* o2 = k2.boxes + ((long)b * maxo + k) * 4;
+        o2[0] = bx[0]; o2[1] = bx[1]; o2[2] = bx[2]; o2[3] = bx[3];
+      }
+      if (k2.scores) k2.scores[(long)b * maxo + k] = ns[(long)b * maxo + i];
       ++k;
     }
   }
   oc[b] = k;
+  if (k2.count) k2.count[b] = k;
   // the rows past the kept boxes are zero (defined outputs: the caller's buffers are not cleared)
   for (int i = k; i < maxo; ++i) {
     float* o = ob + ((long)b * maxo + i) * 4;
     o[0] = o[1] = o[2] = o[3] = 0.f;
     if (os) os[(long)b * maxo + i] = 0.f;
+    if (k2.boxes) {
+      float* o2 = k2.boxes + ((long)b * maxo + i) * 4;
+      o2[0] = o2[1] = o2[2] = o2[3] = 0.f;
+    }
+    if (k2.scores) k2.scores[(long)b * maxo + i] = 0.f;
   }
 }
 
@@ -1189,8 +1200,9 @@ void def_perm_crops(const float* images, int* info, float* crops, int B, int H, 
 }
 
 void def_filter(const float* nb, const float* ns, const int* nc, int B, int maxo, float H, float W, float thresh,
-                float* ob, int* oc, hipStream_t st, float* os) {
-  hipLaunchKernelGGL(k_def_filter, dim3(cdiv(B, 64)), dim3(64), 0, st, nb, ns, nc, B, maxo, H, W, thresh, ob, oc, os);
+                float* ob, int* oc, hipStream_t st, float* os, DefKeep k2) {
+  hipLaunchKernelGGL(k_def_filter, dim3(cdiv(B, 64)), dim3(64), 0, st, nb, ns, nc, B, maxo, H, W, thresh, ob, oc, os,
+                     k2);
   PHX_LAUNCH_CHECK();
 }
 

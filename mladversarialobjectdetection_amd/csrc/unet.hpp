@@ -75,19 +75,25 @@ void un_add(float* a, const float* b, long n, hipStream_t st);
 // info [B][3] = (source image, flip lr, flip ud); crops [B][P][P][3]
 void def_perm_crops(const float* images, int* info, float* crops, int B, int H, int W, int P, uint64_t seed,
                     int64_t step, int gimg0, hipStream_t st);
+// a second copy of a filter's kept detections, written by the same launch (each pointer optional)
+struct DefKeep {
+  float* boxes = nullptr;
+  float* scores = nullptr;
+  int* count = nullptr;
+};
 // filter_valid_boxes (attack_detection.py:79-94); os (optional) receives the kept scores
 void def_filter(const float* nb, const float* ns, const int* nc, int B, int maxo, float H, float W, float thresh,
-                float* ob, int* oc, hipStream_t st, float* os = nullptr);
+                float* ob, int* oc, hipStream_t st, float* os = nullptr, DefKeep k2 = DefKeep{});
 
 // ---- victim side (api.cpp; the profiler hooks exec.cpp, the serving preprocess api_data.cpp) -----
 // odet_model (attack_detection.py:96-127): frozen-BN forward, person anchors, soft-NMS, clip and
 // filter_valid_boxes; boxes [B][100][4], count [B]
 // train: the call's training flag (drop connect), pass: drop-connect key (0 first, 1 second);
 // score_thresh >= 0: odet_model(images, score_thresh) — the soft-NMS threshold only (0 -> 0.001);
-// scores (optional): the kept boxes' scores [B][100]
+// scores (optional): the kept boxes' scores [B][100]; keep: a second copy of the detections
 void def_first_pass(phx_ctx* ctx, const float* images, int B, int64_t step, int gimg0, float* boxes, int* count,
                     hipStream_t s, bool train = true, int pass = 0, float score_thresh = -1.f,
-                    float* scores = nullptr);
+                    float* scores = nullptr, DefKeep keep = DefKeep{});
 int ctx_image_size(const phx_ctx* ctx);
 // a launch group on the victim context's profiler (phx_profile / phx_profile_report): events on
 // `s` around the group, with its algorithmic FLOPs / bytes; a no-op while profiling is off

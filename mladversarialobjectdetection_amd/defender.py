@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import distributed as ddp
+from . import summaries
 from .attacker import EfficientDetVictim, _pad_boxes, _stream, _withdraw_if_refilled
 from .h5 import read_keras_weights, write_keras_weights
 
@@ -166,8 +167,14 @@ class PatchAttackDefender:
     the trainable variables are the U-Net's."""
 
     def __init__(self, protege_model: EfficientDetVictim, initial_weights=None, protege_config_override=None, *,
-                 eval_patch=None, seed=0, learning_rate=1e-2, max_batch=None, device=None):
-        """eval_patch (attack_detection.py:33, 57-61): the attacker's trained patch for the evaluation
+                 eval_patch=None, seed=0, learning_rate=1e-2, max_batch=None, device=None, visualize_freq=200,
+                 summary_writer=None):
+        """summary_writer (summaries.py; None = no summaries, and no launch beyond the step's own): when
+        set, train_step hands vis_images(True) to it at every step with cur_step % visualize_freq == 0 and
+        test_step vis_images(False) at every such val step (attack_detection.py:198-202); a visualize_freq
+        of 0 or less means never.
+
+        eval_patch (attack_detection.py:33, 57-61): the attacker's trained patch for the evaluation
         branch — a directory holding patch.tiff / scale.txt (PatchAttacker.save_weights), a
         (patch [640,640,3], scale) pair, or a PatchAttacker (its current variables).  Only
         call(training=False) / test_step need it."""
@@ -199,6 +206,10 @@ class PatchAttackDefender:
         self.cur_step = 0
         self.eval_params = None if eval_patch is None else self._eval_params(eval_patch, dev)
         self.eval_loss = torch.zeros(1, device=dev)
+        self.visualize_freq = visualize_freq
+        self.summary_writer = summary_writer
+        self._val_step = 0
+        self._last_B = None  # batch size of the last call (vis_images)
 
     @staticmethod
     def _eval_params(eval_patch, dev):
@@ -247,6 +258,7 @@ class PatchAttackDefender:
         placement."""
         images = self.protege_model._check_images(images)
         B = images.shape[0]
+        self._last_B = B
         if boxes is not None:
             bx, cnt = _pad_boxes(boxes, B, images.device)
             if bx.shape[1] != _lib.MAX_OUT:
@@ -291,6 +303,46 @@ class PatchAttackDefender:
         if rc != 0:
             raise _lib.PhxError(f"phx_adam failed ({rc})")
 
+    def summary(self):
+        """phx_def_summary for the step just run: (sample uint8 [2B,S,S,3], original (boxes, scores,
+        count), recovered (boxes, scores, count)) as device tensors.  "Original" is the step's first pass
+        (training) or its attacked second pass (evaluation); "recovered" the protege's detections at
+        score_thresh 0 on clip(patched + updates, -1, 1)."""
+        if self._last_B is None:
+            raise _lib.PhxError("summary: no step has run")
+        B, S, dev = self._last_B, self.protege_model.ctx.image_size, self.params.device
+        sample = torch.empty(2 * B, S, S, 3, dtype=torch.uint8, device=dev)
+        det = [(torch.empty(B, _lib.MAX_OUT, 4, device=dev), torch.empty(B, _lib.MAX_OUT, device=dev),
+                torch.empty(B, dtype=torch.int32, device=dev)) for _ in range(2)]
+        self.handle.call("phx_def_summary", self.params.data_ptr(), sample.data_ptr(),
+                         *[t.data_ptr() for d in det for t in d], _stream())
+        return sample, det[0], det[1]
+
+    def vis_images(self, training=True):
+        """PatchAttackDefender.vis_images (attack_detection.py:239-288) for the step just run, as arrays
+        instead of TensorBoard summaries:
+
+        "Sample"  uint8 [2B,S,S,3]: the attacked image b with the original boxes ([0,1,0]) at 2b, the
+                  recovered image clip(patched + updates, -1, 1) with the recovered boxes ([0,0,1]) at
+                  2b + 1, both denormalised
+        "Scores"  (original, recovered): the valid scores of either set flattened in image order
+                  (merge_dims(0, -1)) — what the reference's violin plot shows; the plot itself is host
+                  matplotlib and is not mirrored
+
+        `training` only names the split the hook writes to: the library knows which step ran last.
+        Rank-local, like the reference's (it visualises on one GPU); no collective is issued.
+        Synchronises with the device."""
+        sample, orig, rec = self.summary()
+
+        def flat(d):
+            sc, cnt = d[1].cpu().numpy(), d[2].cpu().numpy()
+            return np.concatenate([sc[b, :cnt[b]] for b in range(len(cnt))] + [np.zeros(0, np.float32)])
+
+        return {"Sample": sample.cpu().numpy(), "Scores": (flat(orig), flat(rec))}
+
+    def _summarise(self, training, step):
+        summaries.write(self.summary_writer, self.vis_images(training), step, "train" if training else "val")
+
     def train_step(self, inputs, boxes=None, next_inputs=None):
         """attack_detection.py:327-336: grads = self(inputs); apply_gradients.  Returns the loss as a
         device scalar (reading it synchronises).  next_inputs: the batch the next train_step will get
@@ -307,6 +359,10 @@ class PatchAttackDefender:
             self.handle.call("phx_def_set_next", nx.data_ptr(), nx.shape[0], self.global_offset(nx.shape[0]))
         self.call(inputs, boxes=boxes)
         del prev
+        # tf.cond(cur_step % visualize_freq == 0, vis_images) inside call (attack_detection.py:198-202)
+        # (a step placed by caller boxes has no first-pass scores to show: no summary)
+        if boxes is None and summaries.due(self.summary_writer, self.cur_step, self.visualize_freq):
+            self._summarise(True, self.cur_step)
         ddp.allreduce_sum_(self._red)
         self.apply_gradients()
         self.cur_step += 1
@@ -316,6 +372,9 @@ class PatchAttackDefender:
         """attack_detection.py:320-326: self(inputs, training=False); the loss metric summed over
         ranks (the one collective; every rank calls it).  Returns ({"loss": float}, detections)."""
         preds = self.call(inputs, training=False, boxes=boxes)
+        if summaries.due(self.summary_writer, self._val_step, self.visualize_freq):
+            self._summarise(False, self._val_step)
+        self._val_step += 1
         ddp.allreduce_sum_(self.eval_loss)
         return {"loss": float(self.eval_loss.item())}, preds
 
