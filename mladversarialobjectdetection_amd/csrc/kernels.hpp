@@ -408,6 +408,15 @@ size_t soft_nms_work_floats(int B, int N);
 void launch_image_max(const float* scores, const uint8_t* keep, int B, int A, float* m,
                       int* argmax, int* nties, int* scratch, hipStream_t s);
 size_t image_max_scratch_ints(int B);
+// read-only view of the post-processing launch plans (kernels_post.hip), for the parity harness: the
+// pre_nms tile (anchors per workgroup), the chunks of the per-image max, and soft-NMS's plan for N
+// candidates per image (chunk factor, LDS-resident positions, fast path's sort size and re-queue rows
+// under the PHX_NMS_FAST in force, dynamic LDS bytes), its kept decay factors per row candidate and batch size
+struct PostPlanInfo {
+  int pre_tile, imax_chunks;
+  int nms_m, nms_cap, nms_lp, nms_qrows, nms_lds, nms_fl, nms_top_want;
+};
+PostPlanInfo post_plan_info(int N);
 
 // ---- input pipeline (kernels_data.hip, train_data_generator.py) -----------------------------
 // DataSequence._map_fn for B packed uint8 RGB images (offsets [B] bytes, dims [B,2] = (h, w), device)

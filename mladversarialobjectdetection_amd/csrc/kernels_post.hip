@@ -1149,6 +1149,21 @@ __global__ void k_image_max_merge(const float* __restrict__ pm, const int* __res
 
 size_t image_max_scratch_ints(int B) { return (size_t)B * kImaxChunks * 3; }
 
+PostPlanInfo post_plan_info(int N) {
+  const NmsPlan p = nms_plan(N);
+  PostPlanInfo i;
+  i.pre_tile = kPreTile;
+  i.imax_chunks = kImaxChunks;
+  i.nms_m = p.m;
+  i.nms_cap = p.cap;
+  i.nms_lp = p.lp;
+  i.nms_qrows = p.qrows;
+  i.nms_lds = p.lds;
+  i.nms_fl = kNmsFl;
+  i.nms_top_want = kNmsTopWant;
+  return i;
+}
+
 void launch_image_max(const float* scores, const uint8_t* keep, int B, int A, float* m, int* argmax,
                       int* nties, int* scratch, hipStream_t s) {
   float* pm = reinterpret_cast<float*>(scratch);
