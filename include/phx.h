@@ -194,6 +194,19 @@ int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const in
               float* out_boxes, float* out_scores, float* out_classes, int32_t* out_count,
               float* out_scales, void* stream);
 
+/* The person rows of phx_serve's outputs, on the device: Detector.infer's loop (detector.py:48-57)
+ * followed by util.filter_by_thresh (util.py:163-174), and the score the demos report (demo.py:81,
+ * max(sc) before the * 100.).  boxes [B,100,4], scores [B,100], classes [B,100] float32, valid [B]
+ * are phx_serve's outputs (device).  best [B] = the fp32 maximum score over all rows below valid[b]
+ * whose class is 1, thresholded or not; 0 when there is none.  pboxes [B,100,4] = the rows with
+ * class 1 and score >= (float)min_score_thresh (an fp32 compare, as numpy's float32 >= Python
+ * float), compacted in NMS order, zero at and beyond pcount [B].  Rows at and beyond valid[b] are
+ * never read.  boxes and pboxes are 16-byte aligned and do not alias.  One wave per frame, no
+ * atomics: the result is deterministic.  Allocates nothing and does not synchronise. */
+int phx_persons(phx_ctx* ctx, const float* boxes, const float* scores, const float* classes,
+                const int32_t* valid, int B, double min_score_thresh, float* pboxes, int32_t* pcount,
+                float* best, void* stream);
+
 /* ---- EOT patch pipeline ----------------------------------------------------------------- */
 /* BrightnessMatcher.call((src, tgt)) (brightness_matcher.py:43-73) for one src per image:
  * src [B,P,P,3], tgt [B,H,W,3] -> out [B,P,P,3]. */
@@ -355,6 +368,29 @@ int phx_augment(phx_ctx* ctx, const float* in, int B, int H, int W, int64_t step
 int phx_adv_patch(phx_ctx* ctx, uint8_t* images, int B, int H, int W, const float* boxes, const int32_t* count,
                   int max_boxes, const uint8_t* patch, int patch_size, double scale, int out_h, int out_w,
                   int64_t step, int global_image_offset, void* stream);
+
+/* phx_adv_patch with the boxes on the device: the three composites of the demos' loop
+ * (demo.py:116, 177 on the boxes of demo.py:72-76) without a host round trip.  Same contract and the
+ * same bytes as phx_adv_patch for the same boxes, step and global_image_offset, except:
+ *  - boxes [B,max_boxes,4] and count [B] are DEVICE pointers (e.g. phx_persons' pboxes / pcount);
+ *  - rounds (host) is the number of paste rounds issued: box k of every frame is pasted in round k,
+ *    so rounds >= the largest count pastes everything (phx_adv_patch derives it from its host counts);
+ *  - status [B] int32 (device) is overwritten with PHX_AP_* bits.  What phx_adv_patch refuses with
+ *    PHX_EINVAL cannot be seen on the host here: such a box is not pasted (the frame's other boxes
+ *    are) and its frame's status says why.
+ * The placements (AdversarialPatch._create, adv_patch.py:60-91) are computed by a kernel with the host
+ * path's arithmetic; a frame without a box in a round skips that round's brightness sum.  Does not
+ * synchronise and keeps no host table; the first call (or a larger B, rounds or patch) allocates the
+ * scratch it shares with phx_adv_patch (synchronous). */
+enum {
+  PHX_AP_REFUSED = 1,   /* a box's patch side is below 1 pixel or beyond the frame: not pasted */
+  PHX_AP_OVERFLOW = 2,  /* the frame has a box in a slot >= rounds: not pasted                 */
+  PHX_AP_BADCOUNT = 4,  /* count[b] outside [0, max_boxes]: clamped                           */
+};
+int phx_adv_patch_dev(phx_ctx* ctx, uint8_t* images, int B, int H, int W, const float* boxes,
+                      const int32_t* count, int max_boxes, int rounds, const uint8_t* patch, int patch_size,
+                      double scale, int out_h, int out_w, int64_t step, int global_image_offset,
+                      int32_t* status, void* stream);
 
 /* Per-launch-group device timing (HIP events on the launch stream).  enable=1 clears and
  * starts recording; phx_profile_report synchronises and writes JSON

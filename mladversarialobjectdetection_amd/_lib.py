@@ -25,6 +25,8 @@ NMETRIC = 9
 BN_LOCAL, BN_FROZEN, BN_SYNC = 0, 1, 2
 DTYPE_F32, DTYPE_BF16 = 0, 1
 MATCH_MEAN, MATCH_HISTOGRAM = 0, 1
+# phx_adv_patch_dev status bits (phx.h PHX_AP_*)
+AP_REFUSED, AP_OVERFLOW, AP_BADCOUNT = 1, 2, 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PHX_LIB selects another in-tree build (libphx*.so next to this file) for A/B timing runs
@@ -76,6 +78,9 @@ _SIGS = [
       c_void_p, c_void_p]),
     ("phx_serve", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the person rows of phx_serve's device outputs (everything but B and the threshold is a device pointer)
+    ("phx_persons", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_brightness_match", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("phx_set_matcher", c_int, [c_void_p, c_int]),
@@ -108,6 +113,10 @@ _SIGS = [
     ("phx_adv_patch", c_int,
      [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, c_int, c_int,
       c_int64, c_int, c_void_p]),
+    # the same with device boxes / count, host rounds and a device status
+    ("phx_adv_patch_dev", c_int,
+     [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_int,
+      c_int, c_int64, c_int, c_void_p, c_void_p]),
     ("phx_profile", c_int, [c_void_p, c_int]),
     ("phx_profile_report", c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_size_t)]),
     ("phx_debug_last_patched", c_int, [c_void_p, c_void_p, c_void_p]),

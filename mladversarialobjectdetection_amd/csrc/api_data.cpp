@@ -1,5 +1,5 @@
 // api_data.cpp — libphx C ABI, the serving and data entry points: phx_serve*, phx_nms_global, the
-// patch-to-scene matchers, phx_letterbox, phx_augment, phx_adv_patch, phx_patch_images.
+// patch-to-scene matchers, phx_persons, phx_letterbox, phx_augment, phx_adv_patch(_dev), phx_patch_images.
 #include "ctx.hpp"
 
 namespace {
@@ -188,6 +188,23 @@ int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const in
   PHX_CATCH(ctx)
 }
 
+int phx_persons(phx_ctx* ctx, const float* boxes, const float* scores, const float* classes, const int32_t* valid,
+                int B, double min_score_thresh, float* pboxes, int32_t* pcount, float* best, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  if (B < 1) return fail(ctx, PHX_EINVAL, "persons: B must be >= 1");
+  if (!boxes || !scores || !classes || !valid || !pboxes || !pcount || !best)
+    return fail(ctx, PHX_EINVAL, "persons: null boxes, scores, classes, valid or output pointer");
+  if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(pboxes)) & 15)
+    return fail(ctx, PHX_EINVAL, "persons: boxes and pboxes must be 16-byte aligned");
+  if (boxes == pboxes) return fail(ctx, PHX_EINVAL, "persons: boxes and pboxes alias");
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  launch_persons(boxes, scores, classes, valid, B, (float)min_score_thresh, PHX_MAX_OUT, pboxes, pcount, best,
+                 (hipStream_t)stream);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
 int phx_brightness_match(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W,
                          int B, float* out, void* stream) {
   if (!ctx || !src || !tgt || !out || B <= 0 || B > ctx->max_batch) return PHX_EINVAL;
@@ -370,6 +387,53 @@ int phx_adv_patch(phx_ctx* ctx, uint8_t* images, int B, int H, int W, const floa
   }
   // the host table must outlive its (pageable, staged) copy
   PHX_HIP(hipStreamSynchronize(s));
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_adv_patch_dev(phx_ctx* ctx, uint8_t* images, int B, int H, int W, const float* boxes, const int32_t* count,
+                      int max_boxes, int rounds, const uint8_t* patch, int patch_size, double scale, int out_h,
+                      int out_w, int64_t step, int global_image_offset, int32_t* status, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  if (!images || !boxes || !count || !patch || !status || B <= 0 || H <= 0 || W <= 0 || max_boxes < 0 ||
+      patch_size <= 0 || out_h <= 0 || out_w <= 0)
+    return fail(ctx, PHX_EINVAL, "adv_patch_dev: null pointer or empty shape");
+  if (rounds < 0) return fail(ctx, PHX_EINVAL, "adv_patch_dev: rounds is negative");
+  if ((long)B * std::max(max_boxes, rounds) > (1L << 30))
+    return fail(ctx, PHX_EINVAL, "adv_patch_dev: B * max(max_boxes, rounds) exceeds 2^30");
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int P = patch_size;
+  // the rescale of AdversarialPatch.rescale (adv_patch.py:93-108)
+  const double sc = std::min((double)out_w / W, (double)out_h / H);
+  const int sh = (int)(H * sc), sw = (int)(W * sc);
+  if (sh < 1 || sw < 1) throw std::invalid_argument("adv_patch_dev: the rescaled image is empty");
+  // phx_adv_patch's scratch and layout: [ysum B | ysrc 1 | table rounds x B | printed P x P x 3]
+  const size_t ntab = (size_t)std::max(rounds, 1) * B;
+  const size_t need = (size_t)P * P * 3 + sizeof(unsigned long long) * (1 + (size_t)B) + sizeof(ApBox) * ntab + 64;
+  if (need > ctx->ap_cap) {
+    PHX_HIP(hipStreamSynchronize(s));
+    ctx->ap_ws.reset(dalloc<char>(need));
+    ctx->ap_cap = need;
+  }
+  char* ws = static_cast<char*>(ctx->ap_ws.get());
+  auto* ysum = reinterpret_cast<unsigned long long*>(ws);
+  auto* ysrc = ysum + B;
+  auto* dtab = reinterpret_cast<ApBox*>(ysrc + 1);
+  uint8_t* printed = reinterpret_cast<uint8_t*>(dtab + ntab);
+  PHX_HIP(hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), s));
+  launch_ap_place(boxes, count, B, max_boxes, rounds, H, W, scale, dtab, status, s);
+  launch_ap_print(patch, printed, P, ysrc, s);
+  // a patch is square and fits the frame: no round has more than min(H, W)^2 pixels; the paste grid is
+  // sized for that and a workgroup beyond its frame's ph * pw (or of a frame without a box) exits at once
+  const int side = std::min(H, W);
+  const int max_pix = (int)std::min<long>((long)side * side, 1L << 30);
+  for (int k = 0; k < rounds; ++k) {
+    launch_ap_ysum(images, B, H, W, out_h, out_w, sh, sw, ysum, s, dtab + (size_t)k * B);
+    launch_ap_paste(images, B, H, W, printed, P, dtab + (size_t)k * B, max_pix, k, ysum, ysrc, out_h, out_w,
+                    ctx->seed, step, global_image_offset, s);
+  }
   return PHX_OK;
   PHX_CATCH(ctx)
 }

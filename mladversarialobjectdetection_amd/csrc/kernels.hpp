@@ -439,6 +439,10 @@ void launch_serve_preprocess(const uint8_t* src, const ServeFrame* frames_dev, i
 // float, boxes *= scales[b] (scales may be null); rows >= count[b] get class 0
 void launch_nms_global_epilogue(const int* sel, const int* count, const int* classes, const float* scales, int B,
                                 int N, int max_out, float* boxes, float* out_classes, hipStream_t s);
+// person rows of phx_serve's outputs: pboxes [B,max_out,4] compacted in NMS order (zero beyond pcount),
+// best [B] = max score of every class-1 row below valid (0 without one)
+void launch_persons(const float* boxes, const float* scores, const float* classes, const int* valid, int B,
+                    float thresh, int max_out, float* pboxes, int* pcount, float* best, hipStream_t s);
 // one frame of a recovery call (demo_v2.py:151-169), sized on the host
 struct RecFrame {
   int64_t out_off;  // element offset of the recovered frame in out_u8 / out_f32
@@ -466,8 +470,13 @@ struct ApBox {
 // printed = (raw + 127) >> 1 per byte ([P,P,3]); *ysum = sum of its Y (zeroed first)
 void launch_ap_print(const uint8_t* raw, uint8_t* printed, int P, unsigned long long* ysum, hipStream_t s);
 // ysum[b] = sum of Y over the out_h x out_w rescale of image b (its sh x sw content + grey letterbox)
+// (boxes: the round's device placements, or null; a frame whose entry is not valid is skipped)
 void launch_ap_ysum(const uint8_t* img, int B, int H, int W, int out_h, int out_w, int sh, int sw,
-                    unsigned long long* ysum, hipStream_t s);
+                    unsigned long long* ysum, hipStream_t s, const ApBox* boxes = nullptr);
+// tab [rounds,B] from device boxes [B,max_boxes,4] / count [B]; status [B] (zeroed by the caller) gets
+// the PHX_AP_* bits (include/phx.h) of what was not pasted
+void launch_ap_place(const float* boxes, const int* count, int B, int max_boxes, int rounds, int H, int W,
+                     double scale, ApBox* tab, int* status, hipStream_t s);
 // paste round `slot`: boxes[b] for every image (device), max_pix = largest ph * pw of the round
 void launch_ap_paste(uint8_t* img, int B, int H, int W, const uint8_t* printed, int P, const ApBox* boxes,
                      int max_pix, int slot, const unsigned long long* ysum, const unsigned long long* ysrc, int out_h,

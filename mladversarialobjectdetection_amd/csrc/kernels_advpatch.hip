@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "phx.h"
 
 namespace phx {
 
@@ -126,8 +127,10 @@ __global__ __launch_bounds__(256) void k_ap_print(const uint8_t* __restrict__ ra
 // the grey letterbox (127, 127, 127) has Y = 127: `grey` = 127 * its pixel count
 __global__ __launch_bounds__(256) void k_ap_ysum(const uint8_t* __restrict__ img, int H, int W, int sh, int sw,
                                                  int mode, double sy, double sx, unsigned long long grey,
-                                                 unsigned long long* __restrict__ ysum) {
+                                                 unsigned long long* __restrict__ ysum,
+                                                 const ApBox* __restrict__ boxes) {
   const int b = blockIdx.y;
+  if (boxes && !boxes[b].valid) return;  // (device placements) no paste will read this frame's sum
   if (blockIdx.x == 0 && threadIdx.x == 0 && grey) atomicAdd(ysum + b, grey);
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   const uint8_t* im = img + (long)b * H * W * 3;
@@ -262,6 +265,56 @@ __global__ __launch_bounds__(256) void k_ap_paste(uint8_t* __restrict__ img, int
   }
 }
 
+// The placement table of phx_adv_patch_dev: AdversarialPatch._create (adv_patch.py:60-91) for boxes and
+// counts that live on the device, one thread per (frame, slot), the arithmetic of phx_adv_patch's host
+// loop operation for operation (this file is compiled with -ffp-contract=off): h, w as fp32 differences
+// widened to double, pw = (int)(max(h, w) * scale), centre, clamp to 0 and shift to H - ph / W - pw in
+// double, truncation.  tab [rounds,B]: every entry is written (valid = 0 where the frame has no box in
+// that round).  What the host path refuses is not pasted here and reported in status[b] (zeroed by the
+// caller): PHX_AP_REFUSED for a side below 1 or beyond the frame, PHX_AP_OVERFLOW for a box in a slot
+// >= rounds, PHX_AP_BADCOUNT for a count outside [0, max_boxes] (clamped).  atomicOr on one word: the
+// result does not depend on the order.  Latency-trivial.
+__global__ __launch_bounds__(64) void k_ap_place(const float* __restrict__ boxes, const int* __restrict__ count, int B,
+                                                 int max_boxes, int rounds, int slots, int H, int W, double scale,
+                                                 ApBox* __restrict__ tab, int* __restrict__ status) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= B * slots) return;
+  const int b = t / slots, k = t - b * slots;
+  const int raw = count[b];
+  const int n = min(max(raw, 0), max_boxes);
+  if (k == 0 && raw != n) atomicOr(status + b, PHX_AP_BADCOUNT);
+  ApBox e{0, 0, 0, 0, 0};
+  if (k < n) {
+    if (k >= rounds) {
+      atomicOr(status + b, PHX_AP_OVERFLOW);
+    } else {
+      const float* q = boxes + ((long)b * max_boxes + k) * 4;
+      const double ymin = q[0], xmin = q[1];
+      const double h = (float)(q[2] - q[0]), w = (float)(q[3] - q[1]);
+      const double long_side = fmax(h, w);
+      const int pw = (int)(long_side * scale), ph = pw;
+      if (ph < 1 || ph > H || pw > W) {
+        atomicOr(status + b, PHX_AP_REFUSED);
+      } else {
+        double ymp = fmax((ymin + h / 2.0) - ph / 2.0, 0.0), xmp = fmax((xmin + w / 2.0) - pw / 2.0, 0.0);
+        if (ymp + ph > H) ymp = H - ph;
+        if (xmp + pw > W) xmp = W - pw;
+        e = ApBox{1, (int)ymp, (int)xmp, ph, pw};
+      }
+    }
+  }
+  if (k < rounds) tab[(long)k * B + b] = e;
+}
+
+void launch_ap_place(const float* boxes, const int* count, int B, int max_boxes, int rounds, int H, int W,
+                     double scale, ApBox* tab, int* status, hipStream_t s) {
+  const int slots = max_boxes > rounds ? max_boxes : rounds;
+  if (slots <= 0) return;
+  hipLaunchKernelGGL(k_ap_place, dim3(cdiv(B * slots, 64)), dim3(64), 0, s, boxes, count, B, max_boxes, rounds, slots,
+                     H, W, scale, tab, status);
+  PHX_LAUNCH_CHECK();
+}
+
 void launch_ap_print(const uint8_t* raw, uint8_t* printed, int P, unsigned long long* ysum, hipStream_t s) {
   const int n = P * P;
   PHX_HIP(hipMemsetAsync(ysum, 0, sizeof(unsigned long long), s));
@@ -270,13 +323,13 @@ void launch_ap_print(const uint8_t* raw, uint8_t* printed, int P, unsigned long 
 }
 
 void launch_ap_ysum(const uint8_t* img, int B, int H, int W, int out_h, int out_w, int sh, int sw,
-                    unsigned long long* ysum, hipStream_t s) {
+                    unsigned long long* ysum, hipStream_t s, const ApBox* boxes) {
   PHX_HIP(hipMemsetAsync(ysum, 0, (size_t)B * sizeof(unsigned long long), s));
   const int mode = (sh == H && sw == W) ? 0 : (H == 2 * sh && W == 2 * sw) ? 1 : 2;
   const double sy = 1.0 / ((double)sh / (double)H), sx = 1.0 / ((double)sw / (double)W);
   const unsigned long long grey = 127ull * (unsigned long long)((long)out_h * out_w - (long)sh * sw);
   hipLaunchKernelGGL(k_ap_ysum, dim3(cdiv((long)sh * sw, 256), B), dim3(256), 0, s, img, H, W, sh, sw, mode, sy,
-                     sx, grey, ysum);
+                     sx, grey, ysum, boxes);
   PHX_LAUNCH_CHECK();
 }
 

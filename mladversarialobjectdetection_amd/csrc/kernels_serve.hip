@@ -211,6 +211,51 @@ void launch_nms_global_epilogue(const int* sel, const int* count, const int* cla
   PHX_LAUNCH_CHECK();
 }
 
+// ---- person selector (detector.py:48-57, util.py:163-174, demo.py:81) --------------------------------
+// k_persons: one wave per frame over phx_serve's 100 rows, in two passes of 64.  A row is a person when
+// it lies below valid[b] and its class is 1; it is kept when its score >= thresh (fp32).  The kept
+// rows' output slot is the number of kept rows before it: the popcount of the ballot's lower lanes plus
+// the first pass's total, so the order is the NMS order and nothing depends on timing (no atomics).
+// best[b] = the maximum score of every person row, kept or not (a butterfly max), 0 without one.
+// Rows of pboxes at and beyond the count are zeroed by the same wave.  Latency-trivial: 2.4 KB per frame.
+__global__ __launch_bounds__(64) void k_persons(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                const float* __restrict__ classes, const int* __restrict__ valid,
+                                                float thresh, int max_out, float* __restrict__ pboxes,
+                                                int* __restrict__ pcount, float* __restrict__ best) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = min(max(valid[b], 0), max_out);
+  const long row0 = (long)b * max_out;
+  const float4* in = reinterpret_cast<const float4*>(boxes) + row0;
+  float4* out = reinterpret_cast<float4*>(pboxes) + row0;
+  int base = 0;
+  bool any = false;
+  float mx = -INFINITY;
+  for (int i0 = 0; i0 < max_out; i0 += 64) {
+    const int i = i0 + lane;
+    const bool person = i < n && classes[row0 + i] == 1.0f;
+    const float sc = person ? scores[row0 + i] : -INFINITY;
+    mx = fmaxf(mx, sc);
+    const bool keep = person && sc >= thresh;
+    const unsigned long long kept = __ballot(keep);
+    any |= __ballot(person) != 0ull;
+    if (keep) out[base + __popcll(kept & ((1ull << lane) - 1ull))] = in[i];
+    base += __popcll(kept);
+  }
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  for (int i = base + lane; i < max_out; i += 64) out[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (lane == 0) {
+    pcount[b] = base;
+    best[b] = any ? mx : 0.f;
+  }
+}
+
+void launch_persons(const float* boxes, const float* scores, const float* classes, const int* valid, int B,
+                    float thresh, int max_out, float* pboxes, int* pcount, float* best, hipStream_t s) {
+  hipLaunchKernelGGL(k_persons, dim3(B), dim3(64), 0, s, boxes, scores, classes, valid, thresh, max_out, pboxes,
+                     pcount, best);
+  PHX_LAUNCH_CHECK();
+}
+
 // ---- recovery epilogue (demo_v2.py:159-168) ----------------------------------------------------------
 // k_def_recover: one launch for a batch of differently sized frames, no [S,S,3] or [d,d,3] intermediate
 // in HBM.  A frame's cropped output [oh,ow,3] is one contiguous run of oh * ow * 3 elements; a lane owns

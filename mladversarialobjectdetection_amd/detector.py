@@ -2,17 +2,19 @@
 
   Detector.infer           detector.py:35-60: one raw uint8 frame of any size -> person boxes in
                            frame pixels and their scores, in NMS order
+  Detector.infer_device    the same followed by util.filter_by_thresh and the demos' max(sc)
+                           (demo.py:72-81), left on the device (phx_serve + phx_persons)
   ServeDriver.serve        infer_lib.KerasDriver.serve (infer_lib.py:408-421) ->
                            EfficientDetModel.call(raw_frames, training=False, pre_mode='infer',
                            post_mode='global') (efficientdet_keras.py:912-994)
   ServeDriver._preprocess  EfficientDetModel._preprocessing(mode='infer') (dataloader.py:59-201)
   filter_by_thresh         util.py:163-174
 
-Everything runs in libphx.so (phx_serve / phx_serve_preprocess / phx_nms_global) on the current
+Everything runs in libphx.so (phx_serve / phx_serve_preprocess / phx_nms_global / phx_persons) on the current
 PyTorch-ROCm stream; there is no CPU fallback.  One deliberate difference: rows at and beyond
 valid_len are zero in every output (TF's padded NonMaxSuppressionV5 repeats candidate 0 there and
 detector.py:51-57 loops over all 100 rows); `infer` reads the first valid_len rows only.
-Not mirrored: __call__ (cv2 drawing), streaming, the demos.
+Not mirrored: __call__ (cv2 drawing), streaming.  The demos' loop is demo.py's ClipEvaluator.
 """
 from __future__ import annotations
 
@@ -166,6 +168,21 @@ class Detector:
         """`infer` for every frame of a batch (<= max_batch) through one phx_serve call."""
         boxes, scores, classes, valid = (t.cpu().numpy() for t in self.driver.serve(frames))
         return [_persons(boxes[b], scores[b], classes[b], valid[b], max_boxes) for b in range(len(valid))]
+
+    def infer_device(self, frames, min_score_thresh):
+        """`infer_batch` + filter_by_thresh without leaving the device: -> (pboxes [B,100,4] the person
+        boxes with score >= float32(min_score_thresh) in NMS order, zero beyond pcount [B] int32;
+        best [B] float32 the best person score of each frame, thresholded or not, 0 without a person:
+        demo.py:81's max(sc) before the * 100.)."""
+        boxes, scores, classes, valid = self.driver.serve(frames)
+        B, dev = valid.shape[0], valid.device
+        pboxes = torch.empty(B, _lib.MAX_OUT, 4, device=dev)
+        pcount = torch.empty(B, dtype=torch.int32, device=dev)
+        best = torch.empty(B, device=dev)
+        self.driver.model.ctx.call("phx_persons", boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(),
+                                   valid.data_ptr(), B, float(min_score_thresh), pboxes.data_ptr(),
+                                   pcount.data_ptr(), best.data_ptr(), _stream())
+        return pboxes, pcount, best
 
 
 def filter_by_thresh(bb, sc, score_thresh):
