@@ -101,7 +101,7 @@ enum {
  * (infer_lib.py:385-403): builds the EfficientDet program for `cfg` on `device`. */
 int phx_create(const phx_config* cfg, int device, phx_ctx** out);
 void phx_destroy(phx_ctx* ctx);
-/* ctx == NULL: the message of this thread's last failed phx_create. */
+/* ctx == NULL: the message of this thread's last failed phx_create or phx_ingest_dims. */
 const char* phx_last_error(const phx_ctx* ctx);
 int phx_abi_version(void);
 /* The effective model configuration as JSON (hparams_config.get_efficientdet_config,
@@ -193,6 +193,41 @@ int phx_nms_global(phx_ctx* ctx, const float* boxes, const float* scores, const 
 int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
               float* out_boxes, float* out_scores, float* out_classes, int32_t* out_count,
               float* out_scales, void* stream);
+
+/* ---- stream ingest (streaming.py:53-62 Stream.change_frame_size, :75 the video path's BGR -> RGB) --
+ * What the reference's streaming.Stream does to every frame before anything else sees it: for one
+ * uint8 frame [h,w,3] and a target width set_width
+ *   scale = set_width / w                       a float64 division
+ *   dh = int(h * scale)                         a truncated float64 product, NOT h * set_width // w:
+ *                                               77x77 at 640 becomes 639x640, 117x78 959x640
+ *   cv2.resize(frame, (set_width, dh))          the default INTER_LINEAR on an 8UC3 frame: equal size
+ *                                               copies, w == 2 set_width and h == 2 dh takes the 2x2 box
+ *                                               mean (sum + 2) >> 2, everything else is the 11-bit
+ *                                               fixed-point bilinear (fx in float32 from a double
+ *                                               expression, horizontal pass into int rows, vertical
+ *                                               ((b0 * (S0 >> 4)) >> 16 + (b1 * (S1 >> 4)) >> 16 + 2) >> 2)
+ * set_width == 0 means no rescaling.  Results are exact (uint8 equality with cv2's arithmetic).
+ *
+ * phx_ingest_dims: the ingest size of B frames, host arithmetic only (no context, nothing launched):
+ * dims [B,2] int32 (h, w) -> out_dims [B,2] (int(h * ((double)set_width / w)), set_width), or the dims
+ * unchanged when set_width is 0.  PHX_EINVAL (message: phx_last_error(NULL)): a null pointer, B < 1,
+ * set_width < 0, h or w < 1, a height that truncates to 0 (cv2.resize raises there) or leaves the int
+ * range. */
+int phx_ingest_dims(int set_width, const int32_t* dims, int B, int32_t* out_dims);
+/* One launch for a packed batch of frames of mixed sizes, passed as for phx_serve (src device; offsets,
+ * dims host).  Frame b is written at out + out_offsets[b] (out device; out_offsets a HOST array of byte
+ * offsets, any alignment) with phx_ingest_dims' size, rows packed; nothing outside the frames is
+ * written.  flags: PHX_INGEST_BGR reads channel 2 - c (the reference's cvtColor BGR2RGB on decoded
+ * video); set_width == 0 copies, with the swap if asked.
+ * Every argument is checked on the host before anything is launched: PHX_EINVAL with a message naming
+ * the argument for what phx_ingest_dims refuses, an unknown flag bit, a negative offset, an output frame
+ * whose bytes overlap any source frame's or another output frame's (as addresses: src + offsets[k] against
+ * out + out_offsets[b]); PHX_ECAP for B > max_batch.  Runs on the caller's stream without synchronising;
+ * the host tables may be freed on return.  Shares phx_serve's frame tables: the first serving or ingest
+ * call reserves them (synchronous), and the host waits only when 8 such calls are still in flight. */
+enum { PHX_INGEST_BGR = 1 };
+int phx_ingest(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B,
+               int set_width, int flags, uint8_t* out, const int64_t* out_offsets, void* stream);
 
 /* The person rows of phx_serve's outputs, on the device: Detector.infer's loop (detector.py:48-57)
  * followed by util.filter_by_thresh (util.py:163-174), and the score the demos report (demo.py:81,

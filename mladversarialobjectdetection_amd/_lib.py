@@ -27,6 +27,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 MATCH_MEAN, MATCH_HISTOGRAM = 0, 1
 # phx_adv_patch_dev status bits (phx.h PHX_AP_*)
 AP_REFUSED, AP_OVERFLOW, AP_BADCOUNT = 1, 2, 4
+INGEST_BGR = 1  # phx_ingest flag (phx.h PHX_INGEST_BGR): read channel 2 - c
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PHX_LIB selects another in-tree build (libphx*.so next to this file) for A/B timing runs
@@ -78,6 +79,10 @@ _SIGS = [
       c_void_p, c_void_p]),
     ("phx_serve", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # stream ingest (offsets / dims / out_offsets are host arrays; phx_ingest_dims takes no context)
+    ("phx_ingest_dims", c_int, [c_int, c_void_p, c_int, c_void_p]),
+    ("phx_ingest", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     # the person rows of phx_serve's device outputs (everything but B and the threshold is a device pointer)
     ("phx_persons", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -205,6 +210,7 @@ class Context:
             msg = lib.phx_last_error(None)
             raise PhxError(f"phx_create({model_name}) failed ({rc}): {msg.decode() if msg else ''}")
         self.h = h
+        self.device = int(device)
         self.model_name = model_name
         self.max_batch = int(max_batch)
         self.image_size = lib.phx_image_size(h)

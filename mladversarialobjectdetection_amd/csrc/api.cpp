@@ -59,9 +59,15 @@ std::vector<float> make_anchors(const ModelConfig& mc) {
   return out;
 }
 
-thread_local std::string g_create_err;  // phx_last_error(NULL): the last failed phx_create
+// phx_last_error(NULL): the last failed phx_create or context-free call (phx_ingest_dims)
+thread_local std::string g_create_err;
 
 }  // namespace
+
+int fail_global(int code, const std::string& msg) {
+  g_create_err = msg;
+  return code;
+}
 
 // phx_model_info: the configuration the program builder used (model.cpp get_model_config) in
 // hparams_config's key names, plus the BiFPN node list (fpn_configs.py:24-72)

@@ -1,4 +1,4 @@
-// api_data.cpp — libphx C ABI, the serving and data entry points: phx_serve*, phx_nms_global, the
+// api_data.cpp — libphx C ABI, the serving and data entry points: phx_serve*, phx_ingest*, phx_nms_global, the
 // patch-to-scene matchers, phx_persons, phx_letterbox, phx_augment, phx_adv_patch(_dev), phx_patch_images.
 #include "ctx.hpp"
 
@@ -37,9 +37,9 @@ std::string serve_frames(const phx_ctx* ctx, const char* fn, const void* src, co
   return "";
 }
 
-// the next slot of the frame-table ring, filled and copied on `s`; the caller records srv_ev[slot]
-// on `s` after the kernel that reads the table
-const ServeFrame* serve_stage(phx_ctx* ctx, const std::vector<ServeFrame>& fr, hipStream_t s, int* slot_out) {
+// the next slot of the frame-table ring (max_batch ServeFrame-sized rows), filled with `bytes` of rows
+// and copied on `s`; the caller records srv_ev[slot] on `s` after the kernel that reads the table
+const void* stage_rows(phx_ctx* ctx, const void* rows, size_t bytes, hipStream_t s, int* slot_out) {
   const size_t slot_frames = (size_t)ctx->max_batch;
   if (!ctx->srv_host) {
     const size_t n = slot_frames * phx_ctx::kSrvRing;
@@ -56,10 +56,32 @@ const ServeFrame* serve_stage(phx_ctx* ctx, const std::vector<ServeFrame>& fr, h
   ctx->srv_busy[slot] = false;
   ServeFrame* h = ctx->srv_host + slot * slot_frames;
   ServeFrame* d = static_cast<ServeFrame*>(ctx->srv_dev.get()) + slot * slot_frames;
-  std::memcpy(h, fr.data(), fr.size() * sizeof(ServeFrame));
-  PHX_HIP(hipMemcpyAsync(d, h, fr.size() * sizeof(ServeFrame), hipMemcpyHostToDevice, s));
+  std::memcpy(h, rows, bytes);
+  PHX_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
   *slot_out = slot;
   return d;
+}
+
+const ServeFrame* serve_stage(phx_ctx* ctx, const std::vector<ServeFrame>& fr, hipStream_t s, int* slot_out) {
+  return static_cast<const ServeFrame*>(stage_rows(ctx, fr.data(), fr.size() * sizeof(ServeFrame), s, slot_out));
+}
+
+// streaming.Stream.change_frame_size's destination size (streaming.py:59-62): scale = set_width / w and
+// h * scale in float64, truncated; set_width 0 = no rescaling.  Returns the refusal's reason ("" = fine).
+std::string ingest_size(int set_width, int h, int w, int* dh, int* dw) {
+  if (h < 1 || w < 1) return "h and w must be >= 1";
+  if (set_width == 0) {
+    *dh = h;
+    *dw = w;
+    return "";
+  }
+  const double scale = (double)set_width / (double)w;
+  const double hs = (double)h * scale;
+  if (hs >= 2147483648.0) return "height int(h * (set_width / w)) exceeds the int range";
+  if ((int)hs < 1) return "height int(h * (set_width / w)) is 0 (cv2.resize raises on an empty size)";
+  *dh = (int)hs;
+  *dw = set_width;
+  return "";
 }
 
 void serve_preprocess(phx_ctx* ctx, const uint8_t* src, const std::vector<ServeFrame>& fr, float* images,
@@ -110,6 +132,95 @@ int phx_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const int64_t* offset
   PHX_TRY(ctx)
   PHX_HIP(hipSetDevice(ctx->device));
   serve_preprocess(ctx, src, fr, images, scales, (hipStream_t)stream);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_ingest_dims(int set_width, const int32_t* dims, int B, int32_t* out_dims) {
+  if (!dims) return fail_global(PHX_EINVAL, "ingest_dims: dims is null");
+  if (!out_dims) return fail_global(PHX_EINVAL, "ingest_dims: out_dims is null");
+  if (B < 1) return fail_global(PHX_EINVAL, "ingest_dims: B = " + std::to_string(B) + " must be >= 1");
+  if (set_width < 0)
+    return fail_global(PHX_EINVAL, "ingest_dims: set_width = " + std::to_string(set_width) + " is negative");
+  for (int b = 0; b < B; ++b) {
+    int dh = 0, dw = 0;
+    const int h = dims[2 * b], w = dims[2 * b + 1];
+    const std::string why = ingest_size(set_width, h, w, &dh, &dw);
+    if (!why.empty())
+      return fail_global(PHX_EINVAL, "ingest_dims: dims[" + std::to_string(b) + "] = " + std::to_string(h) + "x" +
+                                         std::to_string(w) + ": " + why);
+    out_dims[2 * b] = dh;
+    out_dims[2 * b + 1] = dw;
+  }
+  return PHX_OK;
+}
+
+int phx_ingest(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const int32_t* dims, int B, int set_width,
+               int flags, uint8_t* out, const int64_t* out_offsets, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  // every check is host arithmetic: a refused call has launched nothing
+  auto refuse = [&](int code, const std::string& msg) { return fail(ctx, code, "ingest: " + msg); };
+  if (B < 1) return refuse(PHX_EINVAL, "B = " + std::to_string(B) + " must be >= 1");
+  if (B > ctx->max_batch)
+    return refuse(PHX_ECAP, "B = " + std::to_string(B) + " exceeds max_batch = " + std::to_string(ctx->max_batch));
+  if (!src) return refuse(PHX_EINVAL, "src is null");
+  if (!offsets) return refuse(PHX_EINVAL, "offsets is null");
+  if (!dims) return refuse(PHX_EINVAL, "dims is null");
+  if (!out) return refuse(PHX_EINVAL, "out is null");
+  if (!out_offsets) return refuse(PHX_EINVAL, "out_offsets is null");
+  if (set_width < 0) return refuse(PHX_EINVAL, "set_width = " + std::to_string(set_width) + " is negative");
+  if (flags & ~PHX_INGEST_BGR) return refuse(PHX_EINVAL, "flags = " + std::to_string(flags) + " has an unknown bit");
+  std::vector<IngestFrame> fr((size_t)B);
+  struct Range {
+    uintptr_t lo, hi;
+  };
+  std::vector<Range> rs((size_t)B), ro((size_t)B);
+  long max_lanes = 0;
+  double bytes = 0;
+  for (int b = 0; b < B; ++b) {
+    const int h = dims[2 * b], w = dims[2 * b + 1];
+    const std::string at = "dims[" + std::to_string(b) + "] = " + std::to_string(h) + "x" + std::to_string(w);
+    int dh = 0, dw = 0;
+    const std::string why = ingest_size(set_width, h, w, &dh, &dw);
+    if (!why.empty()) return refuse(PHX_EINVAL, at + ": " + why);
+    if (offsets[b] < 0) return refuse(PHX_EINVAL, "offsets[" + std::to_string(b) + "] is negative");
+    if (out_offsets[b] < 0) return refuse(PHX_EINVAL, "out_offsets[" + std::to_string(b) + "] is negative");
+    const int64_t lanes = (int64_t)dh * ((dw + 3) / 4);
+    if (lanes > (int64_t)INT32_MAX - 256) return refuse(PHX_EINVAL, at + ": the resized frame exceeds 2^31 lanes");
+    // byte ranges in the address space (h * w and dh * dw are below 2^62)
+    const int64_t spx = (int64_t)h * w, opx = (int64_t)dh * dw;
+    const uintptr_t slo = reinterpret_cast<uintptr_t>(src) + (uintptr_t)offsets[b];
+    const uintptr_t olo = reinterpret_cast<uintptr_t>(out) + (uintptr_t)out_offsets[b];
+    if (spx > INT64_MAX / 3 || (uintptr_t)(spx * 3) > UINTPTR_MAX - slo || slo < (uintptr_t)offsets[b])
+      return refuse(PHX_EINVAL, at + ": the frame exceeds the address range");
+    if ((uintptr_t)(opx * 3) > UINTPTR_MAX - olo || olo < (uintptr_t)out_offsets[b])
+      return refuse(PHX_EINVAL, at + ": the resized frame exceeds the address range");
+    rs[b] = Range{slo, slo + (uintptr_t)(spx * 3)};
+    ro[b] = Range{olo, olo + (uintptr_t)(opx * 3)};
+    fr[b] = IngestFrame{offsets[b], out_offsets[b], h, w, dh, dw};
+    max_lanes = std::max<long>(max_lanes, lanes);
+    bytes += std::min((double)spx * 3, 12.0 * (double)opx) + 3.0 * (double)opx;
+  }
+  // the kernel reads and writes without an order between lanes: no output frame may touch a source
+  // frame or another output frame
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < B; ++k) {
+      if (ro[b].lo < rs[k].hi && rs[k].lo < ro[b].hi)
+        return refuse(PHX_EINVAL, "out_offsets[" + std::to_string(b) + "]: the output frame overlaps source frame " +
+                                      std::to_string(k));
+      if (k < b && ro[b].lo < ro[k].hi && ro[k].lo < ro[b].hi)
+        return refuse(PHX_EINVAL, "out_offsets[" + std::to_string(b) + "]: the output frame overlaps output frame " +
+                                      std::to_string(k));
+    }
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  Scope scope(ctx, "ingest", 0.0, bytes, s);
+  int slot = 0;
+  const void* d = stage_rows(ctx, fr.data(), fr.size() * sizeof(IngestFrame), s, &slot);
+  launch_ingest(src, out, static_cast<const IngestFrame*>(d), B, max_lanes, (flags & PHX_INGEST_BGR) != 0, s);
+  PHX_HIP(hipEventRecord(ctx->srv_ev[slot], s));
+  ctx->srv_busy[slot] = true;
   return PHX_OK;
   PHX_CATCH(ctx)
 }

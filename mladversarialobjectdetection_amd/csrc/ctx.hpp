@@ -361,6 +361,8 @@ inline int fail(phx_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;
   return code;
 }
+// the same for a call without a context: the message phx_last_error(NULL) returns (api.cpp)
+int fail_global(int code, const std::string& msg);
 
 // PHX_PROF_DETAIL=1: launch groups are split by shape ("gemm fwd M=.. N=.. K=..") for tuning
 inline bool prof_detail() {

@@ -457,6 +457,20 @@ struct RecFrame {
 void launch_def_recover(const float* canvas, const float* updates, const RecFrame* frames_dev, int B, int S,
                         const float* mean, const float* stdv, uint8_t* out_u8, float* out_f32, long max_elems,
                         hipStream_t s);
+// ---- stream ingest (kernels_ingest.hip, streaming.py:53-62) ----------------------------------
+// one frame of an ingest call, sized on the host (phx_ingest_dims); it travels in the serving frame-table
+// ring, so it is no larger than a ServeFrame
+struct IngestFrame {
+  int64_t src_off, out_off;  // byte offsets of the frame in src / of the resized frame in out
+  int h, w;                  // frame size
+  int dh, dw;                // int(h * (set_width / w)), set_width (h, w when set_width is 0)
+};
+static_assert(sizeof(IngestFrame) <= sizeof(ServeFrame), "an IngestFrame must fit a frame-table slot");
+// cv2.resize(frame, (dw, dh)) (8-bit INTER_LINEAR: copy / 2x box / fixed-point bilinear by the frame's
+// dims) of B frames into out, rows packed; bgr: channel c is read from 2 - c.  max_lanes = the largest
+// dh * ceil(dw / 4) of the batch (< 2^31)
+void launch_ingest(const uint8_t* src, uint8_t* out, const IngestFrame* frames_dev, int B, long max_lanes, bool bgr,
+                   hipStream_t s);
 // flip -> RandomFlip -> RandomContrast(.2) -> random_brightness(.2) -> clip; in/out [B,H,W,3]
 size_t augment_scratch_doubles(int B);
 void launch_augment(const float* in, float* out, int B, int H, int W, uint64_t seed, int64_t step,

@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "cv_resize.hpp"
 #include "kernels.hpp"
 #include "phx.h"
 
@@ -45,22 +46,7 @@ struct Match {
   }
 };
 
-// saturate_cast<short>(float): round half to even
-__device__ __forceinline__ int round_short(float x) { return (int)rintf(x); }
-
-// INTER_LINEAR tap of destination index d (resize(): fx in float32 from a double expression)
-__device__ __forceinline__ void lin_tap(int d, double scale, int ssize, bool clamp, int* s, int* w0, int* w1) {
-  const float f0 = (float)__dadd_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), -0.5);
-  int sx = (int)floorf(f0);
-  float f = __fadd_rn(f0, -(float)sx);
-  if (clamp) {
-    if (sx < 0) { f = 0.f; sx = 0; }
-    if (sx >= ssize - 1) { f = 0.f; sx = ssize - 1; }
-  }
-  *s = sx;
-  *w0 = round_short(__fmul_rn(__fadd_rn(1.f, -f), 2048.f));
-  *w1 = round_short(__fmul_rn(f, 2048.f));
-}
+// (round_short and the INTER_LINEAR tap lin_tap: cv_resize.hpp, shared with the stream ingest)
 
 // interpolateCubic (A = -0.75), float32 with every operation rounded
 __device__ __forceinline__ void cubic_coeffs(float x, int* w) {

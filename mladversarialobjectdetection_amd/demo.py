@@ -13,7 +13,9 @@ run, their running means, the attack success rate and the attack detection rate.
                                      phx_serve + phx_persons (Detector.infer_device), phx_adv_patch_dev
                                      (AdversarialPatch.add_adv_to_images with device boxes),
                                      phx_def_recover (Recovery.recover); the scores are read back once,
-                                     at the end of the clip, and fed to the three classes in frame order
+                                     at the end of the clip, and fed to the three classes in frame order;
+                                     run_stream takes the raw frames of a streaming.Stream, resized on
+                                     the device as the demos' Stream does (demo.py:284, demo_v2.py:202)
 
 Arithmetic of the bookkeeping: a frame's score is its best person score as float32 times float32(100)
 (the reference's np.float32 * 100. under NumPy's scalar promotion), the threshold is
@@ -24,8 +26,8 @@ float32 until the first frame without a person appends a Python 0., and in float
 calc_asr / calc_adr on an empty queue (no frame with a clean detection above the threshold yet) return
 None; the reference divides by zero there and only ever calls them after an append, as ClipEvaluator does.
 
-Out of scope: cv2 drawing and text, make_graph, the 2x2 mosaic, video I/O and `streaming`, demo_v2's
-flash colour.  There is no CPU fallback: the library must be present.
+Out of scope: cv2 drawing and text, make_graph, the 2x2 mosaic, video decode, the webcam and the
+VideoWriter (streaming's resize is streaming.py's Stream), demo_v2's flash colour.  There is no CPU fallback: the library must be present.
 """
 from __future__ import annotations
 
@@ -189,6 +191,28 @@ class ClipEvaluator:
         n, h, w, _ = batch.shape
         return PackedFrames(batch.reshape(-1), np.arange(n, dtype=np.int64) * (h * w * 3),
                             np.tile(np.asarray([[h, w]], np.int32), (n, 1)))
+
+    def run_stream(self, stream, *, rounds=None, keep_frames=False) -> ClipResult:
+        """`run` on the frames of a streaming.Stream: raw frames of any size, resized on the device to the
+        stream's set_width in batches of max_batch (one upload and one phx_ingest each; a stream without a
+        ctx uses the detector's) and gathered into one device [N,dh,dw,3] tensor — 3 * dh * dw bytes of
+        device memory per frame of the clip, held until `run` returns.  The demos assume one frame size
+        (np.concatenate, a VideoWriter sized from the first frame): a frame whose ingested size differs
+        from the first's raises ValueError naming its index, before any bookkeeping object is touched."""
+        from .streaming import unpack_device
+        ctx = stream.ctx or self.dct_obj.driver.model.ctx
+        clip, first, i = [], None, 0
+        for p in stream.batches(self.max_batch, ctx=ctx):
+            for (dh, dw), fr in zip(p.dims, unpack_device(p)):
+                first = first or (int(dh), int(dw))
+                if (int(dh), int(dw)) != first:
+                    raise ValueError(f"ClipEvaluator.run_stream: frame {i} is {int(dh)}x{int(dw)} after the ingest, "
+                                     f"the clip's first frame {first[0]}x{first[1]}")
+                clip.append(fr)
+                i += 1
+        if not clip:
+            raise ValueError("ClipEvaluator.run_stream: the stream has no frames")
+        return self.run(torch.stack(clip), rounds=rounds, keep_frames=keep_frames)
 
     def run(self, frames, *, rounds=None, keep_frames=False) -> ClipResult:
         """frames [N,h,w,3] uint8 (numpy or a device tensor).  rounds: the paste rounds per batch (an

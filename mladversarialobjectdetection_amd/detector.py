@@ -14,7 +14,8 @@ Everything runs in libphx.so (phx_serve / phx_serve_preprocess / phx_nms_global 
 PyTorch-ROCm stream; there is no CPU fallback.  One deliberate difference: rows at and beyond
 valid_len are zero in every output (TF's padded NonMaxSuppressionV5 repeats candidate 0 there and
 detector.py:51-57 loops over all 100 rows); `infer` reads the first valid_len rows only.
-Not mirrored: __call__ (cv2 drawing), streaming.  The demos' loop is demo.py's ClipEvaluator.
+Not mirrored: __call__ (cv2 drawing).  The demos' loop is demo.py's ClipEvaluator, their stream's resize
+streaming.py's Stream.
 """
 from __future__ import annotations
 
