@@ -78,8 +78,10 @@ Gemm2Plan plan_gemm2(int M, int N, int K, int target_wgs, bool bf16 = false, boo
 // image, so an image's result does not depend on how many images share the launch: plan_gemm2's
 // wave-split-K kernel (k_gemm2k: K split over a workgroup's waves) against k_gemm2 (K in order) is
 // chosen for M / n rows where K >= 256 and never for the few-tile K < 256 shapes (k_gemm2's order, which
-// the fused separable conv keeps too), and the column reductions (the SE pools) chunk their rows
-// for a fixed number of images.  Tiles, grids and workspaces still follow the launch.  0 (default): off.
+// the fused separable conv keeps too), the column reductions (the SE pools) chunk their rows
+// for a fixed number of images, and the SE MLP slices its channels (se_plan: the shares of the squeeze
+// product and the excite's lane groups) as for one image.  Tiles, grids and workspaces still follow the
+// launch.  0 (default): off.
 int& gemm_plan_images();
 void gemm2_force_cfg(int wm, int tm, int tn, int splits);  // tools/gemm_bench sweeps only (0 = off)
 void gemm2_force_wsk(int tm, int tn);                       // tools/gemm_bench sweeps only (0 = off, -1 = never)

@@ -810,9 +810,14 @@ constexpr int kSeT = 256;
 struct SePlan {
   int s1, cs1, s2, cs2;
 };
+// The slices are a summation order: k_se_squeeze writes one fp32 share of the squeeze product per slice,
+// k_se_excite adds them, and its lane groups over the hidden units follow cs2.  They are sized for the
+// launch's images, or, in a batch-invariant forward (gemm_plan_images(), kernels.hpp), as for one image
+// whatever the batch: what every launch of 1 to 3 images has always planned.  The grids stay launch-sized
+// (B x s1, B x s2), and s1 * N <= 4C per image keeps the shares inside the scratch tail either way.
 static SePlan se_plan(int B, int C, int N) {
   SePlan p;
-  const int want = std::max(1, 256 / B);
+  const int want = std::max(1, 256 / (gemm_plan_images() >= 1 ? 1 : B));
   // squeeze shares live in the tail of the colred scratch (B*C*2 doubles = B*C*4 floats)
   p.s1 = std::max(1, std::min(std::min(want, cdiv(C, 32)), 4 * C / std::max(N, 1)));
   p.cs1 = cdiv(C, p.s1);
