@@ -109,11 +109,39 @@ int phx_abi_version(void);
  * tf2/fpn_configs.py:166-176): name, backbone_name, image_size, fpn_num_filters,
  * fpn_cell_repeats, box_class_repeats, anchor_scale, num_scales, aspect_ratios, min_level,
  * max_level, act_type, fpn_weight_method, mean_rgb, stddev_rgb, num_classes, survival_prob,
- * fpn_nodes, score_thresh, nms_score_thresh.  Buffer protocol as phx_weight_manifest. */
+ * fpn_nodes, score_thresh, nms_score_thresh (null when a hard NMS keeps every score), nms_method,
+ * nms_iou_thresh, nms_sigma, nms_max_output_size, post_mode.  Buffer protocol as phx_weight_manifest. */
 int phx_model_info(const phx_ctx* ctx, char* buf, size_t cap, size_t* needed);
 /* Config.override({'nms_configs': {'score_thresh': t}}) (hparams_config.py:91-109) after
  * creation: first-pass filter >= t, soft-NMS threshold t (0.001 when t == 0, method gaussian). */
 int phx_set_score_thresh(phx_ctx* ctx, float score_thresh);
+/* The rest of nms_configs (hparams_config.py:258-266), as postprocess.nms reads it (postprocess.py:175-200):
+ *   method PHX_NMS_HARD ('hard', '' or None): NonMaxSuppressionV5 with iou_threshold = "iou_thresh or 0.5"
+ *     (an iou_thresh of 0 means unset), score_threshold = "score_thresh or -inf", soft_nms_sigma 0;
+ *   method PHX_NMS_GAUSSIAN: iou_threshold 1, score_threshold = "score_thresh or 0.001", soft_nms_sigma =
+ *     sigma / 2.
+ * max_output_size selections at most; every output array keeps its [B,100] shape (rows at and beyond the
+ * count are zero), so max_output_size > 100 is refused.  PHX_EINVAL with a message: an unknown method,
+ * max_output_size outside [1, 100], iou_thresh outside [0, 1], sigma not positive and finite.  The thresholds
+ * in force are the same whichever of phx_set_score_thresh and phx_set_nms_config is called first.  Every
+ * NMS of the context follows it: phx_first_pass, the step's first pass and its second-pass ASR counters, the
+ * defender's odet_model, phx_soft_nms, phx_nms_global, phx_nms_per_class and phx_serve.  The step's gradient
+ * does not pass through NMS (the loss reads pre-NMS maxima).  Drops a pending phx_set_next prefetch.  The
+ * default, {PHX_NMS_GAUSSIAN, 0, 0.5, 100}, is the reference's. */
+enum { PHX_NMS_GAUSSIAN = 0, PHX_NMS_HARD = 1 };
+typedef struct phx_nms_config {
+  int32_t method;           /* PHX_NMS_GAUSSIAN | PHX_NMS_HARD */
+  float iou_thresh;         /* hard: the IoU threshold, 0 = unset (0.5) */
+  float sigma;              /* gaussian: the paper's sigma (TF's soft_nms_sigma is half of it) */
+  int32_t max_output_size;  /* 1..PHX_MAX_OUT */
+} phx_nms_config;
+int phx_set_nms_config(phx_ctx* ctx, const phx_nms_config* cfg);
+int phx_get_nms_config(const phx_ctx* ctx, phx_nms_config* cfg);
+/* EfficientDetModel.call's post_mode for phx_serve: PHX_POST_GLOBAL (postprocess_global, the default) or
+ * PHX_POST_PER_CLASS (postprocess_per_class).  phx_get_post_mode returns the mode (PHX_EINVAL: null ctx). */
+enum { PHX_POST_GLOBAL = 0, PHX_POST_PER_CLASS = 1 };
+int phx_set_post_mode(phx_ctx* ctx, int mode);
+int phx_get_post_mode(const phx_ctx* ctx);
 
 /* JSON list of the victim's tensors in blob order: [{"name","shape","offset","kind"}...].
  * kind: "kernel","bias","gamma","beta","moving_mean","moving_variance","wsm".
@@ -183,7 +211,18 @@ int phx_serve_preprocess(phx_ctx* ctx, const uint8_t* src, const int64_t* offset
 int phx_nms_global(phx_ctx* ctx, const float* boxes, const float* scores, const int32_t* classes,
                    const int32_t* count, int B, int N, const float* scales, float* out_boxes,
                    float* out_scores, float* out_classes, int32_t* out_count, void* stream);
-/* The whole call: preprocess, forward, postprocess_global with the frames' image_scale_to_original,
+/* per_class_nms over caller-provided candidates (postprocess.py:409-467), phx_nms_global's sibling: for each
+ * class cid in [0, num_classes) nms(padded=False) under the context's nms_configs over the candidates with
+ * classes == cid (at most max_output_size selections per class); the classes' selections concatenated in class
+ * order, and the max_output_size best by (possibly decayed) score taken, ties to the lower position of that
+ * concatenation (tf.math.top_k); out_count = min(max_output_size, selections of all classes).  Boxes x scales[b]
+ * (NULL: as they are) and NOT clipped (the reference's per-class path has no clip_boxes); classes cid + 1 as
+ * float32.  Arguments and output shapes as phx_nms_global; rows at and beyond out_count are zero. */
+int phx_nms_per_class(phx_ctx* ctx, const float* boxes, const float* scores, const int32_t* classes,
+                      const int32_t* count, int B, int N, const float* scales, float* out_boxes,
+                      float* out_scores, float* out_classes, int32_t* out_count, void* stream);
+/* The whole call: preprocess, forward, postprocess_global (or, after phx_set_post_mode(PHX_POST_PER_CLASS),
+ * postprocess_per_class: boxes not clipped) with the frames' image_scale_to_original,
  * so boxes are in frame pixels.  The forward always runs inference BN from the moving statistics,
  * without drop connect or moving-statistics update, whatever the context's bn_mode (KerasDriver
  * forces is_training_bn=False, infer_lib.py:171).  out_scales [B] (NULL = skip) receives

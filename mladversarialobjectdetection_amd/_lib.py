@@ -40,6 +40,22 @@ class PhxError(RuntimeError):
     pass
 
 
+# phx_nms_config.method / phx_set_post_mode
+NMS_GAUSSIAN, NMS_HARD = 0, 1
+POST_GLOBAL, POST_PER_CLASS = 0, 1
+POST_MODES = {"global": POST_GLOBAL, "per_class": POST_PER_CLASS}
+
+
+class NmsConfigStruct(ctypes.Structure):
+    """phx_nms_config"""
+    _fields_ = [
+        ("method", ctypes.c_int32),
+        ("iou_thresh", c_float),
+        ("sigma", c_float),
+        ("max_output_size", ctypes.c_int32),
+    ]
+
+
 class _Config(ctypes.Structure):
     _fields_ = [
         ("model_name", c_char_p),
@@ -79,6 +95,14 @@ _SIGS = [
       c_void_p, c_void_p]),
     ("phx_serve", c_int,
      [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # nms_configs beyond score_thresh, per-class post-processing
+    ("phx_set_nms_config", c_int, [c_void_p, c_void_p]),
+    ("phx_get_nms_config", c_int, [c_void_p, c_void_p]),
+    ("phx_set_post_mode", c_int, [c_void_p, c_int]),
+    ("phx_get_post_mode", c_int, [c_void_p]),
+    ("phx_nms_per_class", c_int,
+     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p]),
     # stream ingest (offsets / dims / out_offsets are host arrays; phx_ingest_dims takes no context)
     ("phx_ingest_dims", c_int, [c_int, c_void_p, c_int, c_void_p]),
     ("phx_ingest", c_int,
@@ -239,6 +263,35 @@ class Context:
 
     def set_score_thresh(self, t: float):
         self.call("phx_set_score_thresh", float(t))
+
+    def get_nms_config(self) -> dict:
+        """{'method': 'gaussian' | 'hard', 'iou_thresh', 'sigma', 'max_output_size'} as the context holds it
+        (iou_thresh 0 = unset: 0.5 under 'hard')."""
+        c = NmsConfigStruct()
+        self.call("phx_get_nms_config", ctypes.byref(c))
+        return {"method": "hard" if c.method == NMS_HARD else "gaussian", "iou_thresh": float(c.iou_thresh),
+                "sigma": float(c.sigma), "max_output_size": int(c.max_output_size)}
+
+    def set_nms_config(self, method=None, iou_thresh=None, sigma=None, max_output_size=None):
+        """nms_configs' method ('gaussian'; 'hard', '' or None-as-value are passed as 'hard' by the caller),
+        iou_thresh, sigma, max_output_size; an argument left None keeps the context's value."""
+        cur = self.get_nms_config()
+        m = cur["method"] if method is None else method
+        if m not in ("gaussian", "hard"):
+            raise ValueError(f"nms method {m!r}: 'gaussian' or 'hard'")
+        c = NmsConfigStruct(NMS_HARD if m == "hard" else NMS_GAUSSIAN,
+                            cur["iou_thresh"] if iou_thresh is None else float(iou_thresh),
+                            cur["sigma"] if sigma is None else float(sigma),
+                            cur["max_output_size"] if max_output_size is None else int(max_output_size))
+        self.call("phx_set_nms_config", ctypes.byref(c))
+
+    def set_post_mode(self, mode: str):
+        if mode not in POST_MODES:
+            raise ValueError(f"post_mode {mode!r}: 'global' or 'per_class'")
+        self.call("phx_set_post_mode", POST_MODES[mode])
+
+    def get_post_mode(self) -> str:
+        return "per_class" if self.lib.phx_get_post_mode(self.h) == POST_PER_CLASS else "global"
 
     def weight_count(self) -> int:
         return int(self.lib.phx_weight_count(self.h))

@@ -42,8 +42,9 @@ def _stream():
 
 @dataclass
 class NmsConfig:
-    """hparams_config.py:258-266 (+ attacker_train.py:31 override)"""
-    method: str = "gaussian"
+    """hparams_config.py:258-266 (+ attacker_train.py:31 override); mirrors the library context once
+    honour_nms_configs forwards it (VictimConfig.override)"""
+    method: str | None = "gaussian"
     iou_thresh: float | None = None
     score_thresh: float = 0.0
     sigma: float | None = None
@@ -60,11 +61,16 @@ class VictimConfig:
     # the library context this config describes (set by EfficientDetVictim): overrides that change
     # the computation are forwarded to it, as the reference's model.config.override reaches the model
     ctx: object = field(default=None, repr=False, compare=False)
+    # False: nms_configs other than the reference's defaults (method 'gaussian', sigma 0.5, max_output_size
+    # 100) are refused and iou_thresh is ignored, as before the library honoured them.  True: method, iou_thresh,
+    # sigma and max_output_size reach the library context as postprocess.nms reads them.
+    honour_nms_configs: bool = False
 
     def override(self, d: dict, ctx=None):
         """Config.override (hparams_config.py:91-109) for the keys the attack uses.  The values that
-        change the computation are forwarded to the library context (score_thresh); overrides the
-        library does not implement raise instead of diverging silently from the reference."""
+        change the computation are forwarded to the library context (score_thresh; with honour_nms_configs
+        also method, iou_thresh, sigma, max_output_size); overrides the library does not implement raise
+        instead of diverging silently from the reference."""
         ctx = ctx if ctx is not None else self.ctx
         for k, v in d.items():
             if k != "nms_configs":
@@ -75,6 +81,13 @@ class VictimConfig:
                         raise ValueError("config_override: score_thresh needs the victim's library context "
                                          "(a VictimConfig not owned by an EfficientDetVictim)")
                     ctx.set_score_thresh(float(vv))
+                elif kk in ("pyfunc", "max_nms_inputs"):
+                    if vv:
+                        raise ValueError(f"config_override: nms_configs.{kk} = {vv!r} is not built")
+                elif kk == "max_output_size" and vv is not None and vv > 100:
+                    raise ValueError("config_override: max_output_size is fixed at 100")
+                elif kk in ("method", "iou_thresh", "sigma", "max_output_size") and self.honour_nms_configs:
+                    self._forward_nms(ctx, kk, vv)
                 elif kk == "iou_thresh":
                     pass  # unused by the gaussian method: iou_thresh = 1.0 (postprocess.py:184-188)
                 elif kk == "method" and vv != "gaussian":
@@ -83,11 +96,29 @@ class VictimConfig:
                     raise ValueError("config_override: soft-NMS sigma is fixed at the default 0.5")
                 elif kk == "max_output_size" and vv != 100:
                     raise ValueError("config_override: max_output_size is fixed at 100")
-                elif kk not in ("method", "sigma", "max_output_size", "pyfunc", "max_nms_inputs"):
+                elif kk not in ("method", "sigma", "max_output_size"):
                     raise ValueError(f"config_override: unsupported nms_configs key {kk!r}")
-                elif kk in ("pyfunc", "max_nms_inputs") and vv:
-                    raise ValueError(f"config_override: nms_configs.{kk} = {vv!r} is not built")
                 setattr(self.nms_configs, kk, vv)
+
+    @staticmethod
+    def _forward_nms(ctx, key, value):
+        """One of method / iou_thresh / sigma / max_output_size as postprocess.nms reads it (postprocess.py:
+        175-188): method 'hard', '' or None is hard NMS; "iou_thresh or 0.5"; "sigma or 0.5"."""
+        if ctx is None:
+            raise ValueError(f"config_override: {key} needs the victim's library context "
+                             "(a VictimConfig not owned by an EfficientDetVictim)")
+        if key == "method":
+            if value not in ("hard", "", None, "gaussian"):
+                raise ValueError(f"config_override: Inference has invalid nms method {value}")
+            ctx.set_nms_config(method="gaussian" if value == "gaussian" else "hard")
+        elif key == "iou_thresh":
+            ctx.set_nms_config(iou_thresh=float(value or 0.0))  # 0 = unset: the library applies "or 0.5"
+        elif key == "sigma":
+            ctx.set_nms_config(sigma=float(value or 0.5))
+        else:
+            if value is None or int(value) != value or value < 1:
+                raise ValueError(f"config_override: max_output_size = {value!r}: an integer in [1, 100]")
+            ctx.set_nms_config(max_output_size=int(value))
 
 
 class EfficientDetVictim:
@@ -95,7 +126,7 @@ class EfficientDetVictim:
 
     def __init__(self, model_name="efficientdet-d0", weights="synthetic", *, seed=0, image_size=0,
                  max_batch=16, bn_mode="local", score_thresh=0.5, rng_seed=0, device=None,
-                 person_bias=0.0, dtype="f32"):
+                 person_bias=0.0, dtype="f32", honour_nms_configs=False):
         if device is None:
             device = torch.cuda.current_device() if torch.cuda.is_available() else 0
         self.device = device
@@ -126,7 +157,8 @@ class EfficientDetVictim:
         self.load_weights(blob)
         fam = "lite" if "lite" in model_name else "efficientdet"
         self.config = VictimConfig(model_name, self.ctx.image_size, MEAN_RGB[fam], STDDEV_RGB[fam],
-                                   NmsConfig(score_thresh=score_thresh), ctx=self.ctx)
+                                   NmsConfig(score_thresh=score_thresh), ctx=self.ctx,
+                                   honour_nms_configs=bool(honour_nms_configs))
         self.num_anchors = self.ctx.num_anchors
         self.max_batch = max_batch
 
@@ -174,7 +206,7 @@ class EfficientDetVictim:
         return ob, os_, oc
 
     def soft_nms(self, boxes, scores, count=None):
-        """postprocess.nms(padded=True) over [B,N,4] / [B,N] candidates."""
+        """postprocess.nms(padded=True) over [B,N,4] / [B,N] candidates, under the context's nms_configs."""
         boxes = boxes.contiguous().float()
         scores = scores.contiguous().float()
         B, N = scores.shape

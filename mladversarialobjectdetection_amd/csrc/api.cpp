@@ -92,8 +92,13 @@ std::string phx_ctx::model_info() const {
      << ",\"stddev_rgb\":" << arr3(c.stddev_rgb) << ",\"num_classes\":" << c.num_classes
      << ",\"survival_prob\":" << c.survival_prob << ",\"width_coefficient\":" << c.width_coefficient
      << ",\"depth_coefficient\":" << c.depth_coefficient << ",\"score_thresh\":" << filter_thresh
-     << ",\"nms_score_thresh\":" << nms_thresh << ",\"compute_dtype\":\"" << (bf16 ? "bf16" : "f32")
-     << "\",\"fpn_nodes\":[";
+     << ",\"nms_score_thresh\":";
+  // a hard NMS without a score threshold keeps everything ("score_thresh or -inf"): no JSON number
+  if (std::isinf(nms_thresh)) js << "null"; else js << nms_thresh;
+  js << ",\"nms_method\":\"" << (nms_hard() ? "hard" : "gaussian") << "\",\"nms_iou_thresh\":"
+     << nms_params(nms_thresh).iou_thresh << ",\"nms_sigma\":" << nms.sigma << ",\"nms_max_output_size\":"
+     << nms.max_output_size << ",\"post_mode\":\"" << (post_mode == PHX_POST_PER_CLASS ? "per_class" : "global")
+     << "\",\"compute_dtype\":\"" << (bf16 ? "bf16" : "f32") << "\",\"fpn_nodes\":[";
   const int nlev = c.max_level - c.min_level + 1;
   std::map<int, std::vector<int>> ids;
   for (int i = 0; i < nlev; ++i) ids[c.min_level + i] = {i};
@@ -127,7 +132,14 @@ uint64_t phx::ctx_generation(const phx_ctx* ctx) {
   uint32_t f, n;
   std::memcpy(&f, &ctx->filter_thresh, 4);
   std::memcpy(&n, &ctx->nms_thresh, 4);
-  return (ctx->w_ver * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)f << 32 | n);
+  // every NMS setting moves it: what a holder of first-pass results keyed on it computed is stale
+  uint32_t iou, sg;
+  std::memcpy(&iou, &ctx->nms.iou_thresh, 4);
+  std::memcpy(&sg, &ctx->nms.sigma, 4);
+  const uint64_t cfg = ((uint64_t)iou << 32 | sg) ^ ((uint64_t)ctx->nms.method << 40) ^
+                       ((uint64_t)ctx->nms.max_output_size << 48);
+  const uint64_t dflt = ((uint64_t)0x3f000000u) ^ ((uint64_t)PHX_NMS_GAUSSIAN << 40) ^ ((uint64_t)PHX_MAX_OUT << 48);
+  return (ctx->w_ver * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)f << 32 | n) ^ ((cfg ^ dflt) * 0xD6E8FEB86659FD93ull);
 }
 
 void phx::def_first_pass(phx_ctx* ctx, const float* images, int B, int64_t step, int gimg0, float* boxes, int* count,
@@ -142,7 +154,8 @@ void phx::def_first_pass(phx_ctx* ctx, const float* images, int B, int64_t step,
   // odet_model(images, score_thresh) (attack_detection.py:96-127): an explicit threshold replaces
   // the config's for the soft-NMS only ("score_thresh or 0.001", postprocess.py:186-188), while
   // filter_valid_boxes keeps reading self.config's (:79-94)
-  const float nt = score_thresh < 0.f ? -1.f : (score_thresh != 0.f ? score_thresh : 0.001f);
+  // (hard NMS: "score_thresh or -inf", :183)
+  const float nt = score_thresh < 0.f ? ctx->nms_thresh : ctx->nms_thresh_of(score_thresh);
   run_pre_nms(ctx, E, s, 4, nt);  // person anchors only (attack_detection.py:116-121)
   run_nms(ctx, E, 4, E.nms1_boxes, E.nms1_scores, E.nms1_count, s, nt);
   const float S = (float)ctx->mc.image_size;
@@ -259,6 +272,39 @@ int phx_set_score_thresh(phx_ctx* ctx, float t) {
   return PHX_OK;
   PHX_CATCH(ctx)
 }
+
+int phx_set_nms_config(phx_ctx* ctx, const phx_nms_config* cfg) {
+  if (!ctx) return PHX_EINVAL;
+  if (!cfg) return fail(ctx, PHX_EINVAL, "nms_config: null config");
+  if (cfg->method != PHX_NMS_GAUSSIAN && cfg->method != PHX_NMS_HARD)
+    return fail(ctx, PHX_EINVAL, "nms_config: unknown method (PHX_NMS_GAUSSIAN or PHX_NMS_HARD)");
+  if (cfg->max_output_size > PHX_MAX_OUT)
+    return fail(ctx, PHX_EINVAL, "nms_config: max_output_size > 100 (every output array is [B,100]: its shape is part of the ABI)");
+  if (cfg->max_output_size < 1) return fail(ctx, PHX_EINVAL, "nms_config: max_output_size < 1");
+  if (!(cfg->iou_thresh >= 0.f && cfg->iou_thresh <= 1.f)) return fail(ctx, PHX_EINVAL, "nms_config: iou_thresh outside [0, 1]");
+  if (!(cfg->sigma > 0.f) || std::isinf(cfg->sigma)) return fail(ctx, PHX_EINVAL, "nms_config: sigma must be positive and finite");
+  PHX_TRY(ctx)
+  ctx->pre_drop();
+  ctx->set_nms_config(*cfg);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_get_nms_config(const phx_ctx* ctx, phx_nms_config* cfg) {
+  if (!ctx || !cfg) return PHX_EINVAL;
+  *cfg = ctx->nms;
+  return PHX_OK;
+}
+
+int phx_set_post_mode(phx_ctx* ctx, int mode) {
+  if (!ctx) return PHX_EINVAL;
+  if (mode != PHX_POST_GLOBAL && mode != PHX_POST_PER_CLASS)
+    return fail(ctx, PHX_EINVAL, "post_mode: PHX_POST_GLOBAL or PHX_POST_PER_CLASS");
+  ctx->post_mode = mode;
+  return PHX_OK;
+}
+
+int phx_get_post_mode(const phx_ctx* ctx) { return ctx ? ctx->post_mode : PHX_EINVAL; }
 
 int phx_model_info(const phx_ctx* ctx, char* buf, size_t cap, size_t* needed) {
   if (!ctx) return PHX_EINVAL;
@@ -390,14 +436,7 @@ int phx_soft_nms(phx_ctx* ctx, const float* boxes, const float* scores, const in
   if (!ctx || !boxes || !scores || B <= 0 || N <= 0) return PHX_EINVAL;
   PHX_TRY(ctx)
   hipStream_t s = (hipStream_t)stream;
-  const size_t need = soft_nms_work_floats(B, N);
-  if (need > ctx->sn_cap) {
-    PHX_HIP(hipStreamSynchronize(s));
-    ctx->sn_ws.reset(dalloc<float>(need));
-    ctx->sn_cap = need;
-  }
-  launch_soft_nms(boxes, scores, nullptr, 0, count, B, N, ctx->nms_thresh, 0.25f, PHX_MAX_OUT,
-                  (float)ctx->mc.image_size, ob, os, oc, (float*)ctx->sn_ws.get(), s);
+  run_nms_candidates(ctx, boxes, scores, count, B, N, ob, os, oc, nullptr, s);
   return PHX_OK;
   PHX_CATCH(ctx)
 }

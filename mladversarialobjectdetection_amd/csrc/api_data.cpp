@@ -235,12 +235,6 @@ int phx_nms_global(phx_ctx* ctx, const float* boxes, const float* scores, const 
   PHX_TRY(ctx)
   PHX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  const size_t need = soft_nms_work_floats(B, N);
-  if (need > ctx->sn_cap) {
-    PHX_HIP(hipStreamSynchronize(s));
-    ctx->sn_ws.reset(dalloc<float>(need));
-    ctx->sn_cap = need;
-  }
   const size_t nsel = (size_t)B * PHX_MAX_OUT;
   if (nsel > ctx->srv_sel_cap) {
     PHX_HIP(hipStreamSynchronize(s));
@@ -249,9 +243,25 @@ int phx_nms_global(phx_ctx* ctx, const float* boxes, const float* scores, const 
   }
   int* sel = static_cast<int*>(ctx->srv_sel_ws.get());
   // nms(padded=True) on every candidate above the threshold, boxes clipped to [0, S] by the kernel
-  launch_soft_nms(boxes, scores, nullptr, 0, count, B, N, ctx->nms_thresh, 0.25f, PHX_MAX_OUT,
-                  (float)ctx->mc.image_size, ob, os, oc, (float*)ctx->sn_ws.get(), s, NmsCand{}, sel);
+  run_nms_candidates(ctx, boxes, scores, count, B, N, ob, os, oc, sel, s);
   launch_nms_global_epilogue(sel, oc, classes, scales, B, N, PHX_MAX_OUT, ob, ocl, s);
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_nms_per_class(phx_ctx* ctx, const float* boxes, const float* scores, const int32_t* classes,
+                      const int32_t* count, int B, int N, const float* scales, float* ob, float* os, float* ocl,
+                      int32_t* oc, void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  if (B < 1 || N < 1) return fail(ctx, PHX_EINVAL, "nms_per_class: B and N must be >= 1");
+  if (!boxes || !scores || !classes || !ob || !os || !ocl || !oc)
+    return fail(ctx, PHX_EINVAL, "nms_per_class: null boxes, scores, classes or output pointer");
+  PHX_TRY(ctx)
+  PHX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int C = ctx->mc.num_classes;
+  launch_nms_seg_per_class(boxes, scores, classes, count, B, N, C, ctx->nms_params(ctx->nms_thresh), scales, ob, os,
+                           ocl, oc, seg_scratch(ctx, B, N, C, s), s);
   return PHX_OK;
   PHX_CATCH(ctx)
 }
@@ -291,9 +301,18 @@ int phx_serve(phx_ctx* ctx, const uint8_t* src, const int64_t* offsets, const in
   run_forward(ctx, E, E.srv_images, s, 2, 0, 0, false);
   // postprocess_global (postprocess.py:375-406): pre_nms over all classes, nms(padded=True) on every
   // anchor above the threshold, clip to [0, S], x image_scale_to_original, classes + CLASS_OFFSET
-  run_pre_nms(ctx, E, s, -1);
-  run_nms(ctx, E, -1, ob, os, oc, s, -1.f, E.srv_sel);
-  launch_nms_global_epilogue(E.srv_sel, oc, E.classes, E.srv_scales, B, ctx->A, PHX_MAX_OUT, ob, ocl, s);
+  if (ctx->post_mode == PHX_POST_PER_CLASS) {
+    // postprocess_per_class (postprocess.py:470-493): pre_nms, then per_class_nms over every anchor's argmax
+    // class with the frames' image_scale_to_original; no clip_boxes on this path
+    run_pre_nms(ctx, E, s);
+    Scope scope(ctx, "nms_per_class", 0.0, (double)E.B * ctx->A * 5.0, s);
+    launch_nms_seg_per_class(E.boxes, E.scores, E.classes, nullptr, B, ctx->A, ctx->mc.num_classes,
+                             ctx->nms_params(ctx->nms_thresh), E.srv_scales, ob, os, ocl, oc, seg_scratch(ctx, E), s);
+  } else {
+    run_pre_nms(ctx, E, s, -1);
+    run_nms(ctx, E, -1, ob, os, oc, s, kNmsCtxThresh, E.srv_sel);
+    launch_nms_global_epilogue(E.srv_sel, oc, E.classes, E.srv_scales, B, ctx->A, PHX_MAX_OUT, ob, ocl, s);
+  }
   if (out_scales) PHX_HIP(hipMemcpyAsync(out_scales, E.srv_scales, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
   return PHX_OK;
   PHX_CATCH(ctx)

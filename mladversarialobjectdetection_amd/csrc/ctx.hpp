@@ -16,6 +16,7 @@
 #include <sstream>
 #include <string>
 #include <functional>
+#include <limits>
 #include <vector>
 
 #include "common.hpp"
@@ -133,6 +134,8 @@ struct Exec : ExecPlan {
   // soft-NMS's selected anchors [B,100]; reserved by the first phx_serve of this batch size
   float *srv_images = nullptr, *srv_scales = nullptr;
   int* srv_sel = nullptr;
+  // hard / per-class NMS (kernels_nms_seg.hip): reserved by the first such NMS of this batch size
+  float* seg_ws = nullptr;
   double* sync_sums = nullptr;      // bn=sync: [member][C][3] per-channel sums to all-reduce
 
   // deferred moving statistics (a step whose first pass runs beside the second): while defer_mov
@@ -223,6 +226,27 @@ struct phx_ctx {
   // gaussian soft-NMS keeps scores > nms_thresh = score_thresh or 0.001 (postprocess.py:186-188)
   float score_thresh = 0.f;
   float filter_thresh = 0.f, nms_thresh = 0.001f;
+  // nms_configs' method, iou_thresh, sigma and max_output_size (phx_set_nms_config) and the post mode of
+  // phx_serve (phx_set_post_mode).  postprocess.nms (postprocess.py:179-188): hard = IoU threshold
+  // "iou_thresh or 0.5", score threshold "score_thresh or -inf", no decay; gaussian = IoU threshold 1,
+  // "score_thresh or 0.001", soft_nms_sigma = sigma / 2
+  phx_nms_config nms{PHX_NMS_GAUSSIAN, 0.f, 0.5f, PHX_MAX_OUT};
+  int post_mode = PHX_POST_GLOBAL;
+  bool nms_hard() const { return nms.method == PHX_NMS_HARD; }
+  // the NMS score threshold of nms_configs.score_thresh == t under the method in force
+  float nms_thresh_of(float t) const {
+    if (t != 0.f) return t;
+    return nms_hard() ? -std::numeric_limits<float>::infinity() : 0.001f;
+  }
+  // NonMaxSuppressionV5's parameters at NMS score threshold t
+  NmsSegParams nms_params(float t) const {
+    if (nms_hard()) return NmsSegParams{t, nms.iou_thresh != 0.f ? nms.iou_thresh : 0.5f, 0.f, nms.max_output_size};
+    return NmsSegParams{t, 1.0f, nms.sigma * 0.5f, nms.max_output_size};
+  }
+  // scratch of the caller-candidate entry points under hard or per-class NMS (phx_soft_nms, phx_nms_global,
+  // phx_nms_per_class), grown on demand
+  DPtr seg_ws;
+  size_t seg_cap = 0;
   uint64_t seed = 0;
   int matcher = PHX_MATCH_MEAN;  // phx_set_matcher: the attack's patch-to-scene matcher
   std::vector<WeightEntry> weights;
@@ -273,7 +297,11 @@ struct phx_ctx {
   void set_score_thresh(float t) {
     score_thresh = t;
     filter_thresh = t;
-    nms_thresh = t != 0.f ? t : 0.001f;
+    nms_thresh = nms_thresh_of(t);
+  }
+  void set_nms_config(const phx_nms_config& c) {
+    nms = c;
+    nms_thresh = nms_thresh_of(score_thresh);
   }
 
   float* w() const { return reinterpret_cast<float*>(d_w.get()); }
@@ -451,9 +479,16 @@ void run_forward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s, int p
                  bool train = true, bool force_frozen = false);
 // data-gradient of the victim from the sparse class-logit gradient
 void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s);
-void run_pre_nms(phx_ctx* ctx, Exec& E, hipStream_t s, int cand_mask = 0, float nms_t = -1.f);
-void run_nms(phx_ctx* ctx, Exec& E, int keep_mask, float* ob, float* os, int* oc, hipStream_t s, float nms_t = -1.f,
+// nms_t of run_pre_nms / run_nms: the context's NMS score threshold (a hard NMS's may be -inf, so no
+// real value can stand for it)
+constexpr float kNmsCtxThresh = std::numeric_limits<float>::quiet_NaN();
+void run_pre_nms(phx_ctx* ctx, Exec& E, hipStream_t s, int cand_mask = 0, float nms_t = kNmsCtxThresh);
+void run_nms(phx_ctx* ctx, Exec& E, int keep_mask, float* ob, float* os, int* oc, hipStream_t s, float nms_t = kNmsCtxThresh,
              int* sel = nullptr);
+float* seg_scratch(phx_ctx* ctx, Exec& E);
+float* seg_scratch(phx_ctx* ctx, int B, int N, int C, hipStream_t s);
+void run_nms_candidates(phx_ctx* ctx, const float* boxes, const float* scores, const int* count, int B, int N,
+                        float* ob, float* os, int* oc, int* sel, hipStream_t s);
 void check_guards(phx_ctx* ctx, hipStream_t s);
 // PHX_CKSUM diagnostics
 void ck_begin(Exec& E, hipStream_t s);

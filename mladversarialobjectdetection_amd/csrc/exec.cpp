@@ -1033,7 +1033,7 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
 // soft-NMS candidate list (2: the first pass's person/valid/>=thresh, 1: the second pass's
 // person/valid for the ASR metric, 4: person, -1: every anchor (serving, postprocess_global), 0: no
 // list); the run_nms that follows consumes it
-// nms_t: the soft-NMS score threshold of the candidate list (< 0: the context's)
+// nms_t: the NMS score threshold of the candidate list (kNmsCtxThresh: the context's)
 void run_pre_nms(phx_ctx* ctx, Exec& E, hipStream_t s, int cand_mask, float nms_t) {
   const Program& P = E.prog;
   Scope scope(ctx, "pre_nms", 0.0,
@@ -1046,19 +1046,67 @@ void run_pre_nms(phx_ctx* ctx, Exec& E, hipStream_t s, int cand_mask, float nms_
                  E.lev_dev, (int)E.lev.size(), reinterpret_cast<const float*>(ctx->d_anchors.get()),
                  ctx->A, E.B, ctx->mc.num_classes, ctx->mc.num_anchors(), S, S, ctx->filter_thresh,
                  E.scores, E.classes, E.boxes, E.keep, E.ntiles, s,
-                 cand_mask ? NmsCand{E.cand_list, E.cand_count, cand_mask, nms_t < 0.f ? ctx->nms_thresh : nms_t}
+                 cand_mask ? NmsCand{E.cand_list, E.cand_count, cand_mask, std::isnan(nms_t) ? ctx->nms_thresh : nms_t}
                            : NmsCand{},
                  E.tbf(P.cls_out[0]) != 0);
 }
 
-// postprocess.nms with method 'gaussian': sigma 0.5 -> soft_nms_sigma 0.25
+// postprocess.nms under the context's nms_configs (phx_set_nms_config).  gaussian (sigma 0.5 -> soft_nms_sigma
+// 0.25 by default): k_soft_nms, run to 100 selections and cut to max_output_size; hard: the segmented kernel, one
+// segment per image
 void run_nms(phx_ctx* ctx, Exec& E, int keep_mask, float* ob, float* os, int* oc, hipStream_t s,
              float nms_t, int* sel) {
   Scope scope(ctx, "soft_nms", 0.0, (double)E.B * ctx->A * 5.0, s);
-  const float t = nms_t < 0.f ? ctx->nms_thresh : nms_t;
-  launch_soft_nms(E.boxes, E.scores, E.keep, keep_mask, nullptr, E.B, ctx->A, t,
-                  0.25f, PHX_MAX_OUT, (float)ctx->mc.image_size, ob, os, oc, E.nms_ws, s,
-                  NmsCand{E.cand_list, E.cand_count, keep_mask, t}, sel);
+  const float t = std::isnan(nms_t) ? ctx->nms_thresh : nms_t;
+  const NmsSegParams q = ctx->nms_params(t);
+  if (!ctx->nms_hard()) {
+    launch_soft_nms(E.boxes, E.scores, E.keep, keep_mask, nullptr, E.B, ctx->A, t,
+                    q.soft_sigma, PHX_MAX_OUT, (float)ctx->mc.image_size, ob, os, oc, E.nms_ws, s,
+                    NmsCand{E.cand_list, E.cand_count, keep_mask, t}, sel);
+    launch_nms_truncate(ob, os, oc, sel, E.B, q.max_out, s);
+    return;
+  }
+  seg_scratch(ctx, E);
+  launch_nms_seg_global(E.boxes, E.scores, E.keep, keep_mask, nullptr, E.B, ctx->A, q, (float)ctx->mc.image_size, ob,
+                        os, oc, E.seg_ws, s, NmsCand{E.cand_list, E.cand_count, keep_mask, t}, sel);
+}
+
+// the executor's scratch of the segmented NMS (one segment per image, or one per class), reserved at its first use
+float* seg_scratch(phx_ctx* ctx, Exec& E) {
+  if (!E.seg_ws) E.seg_ws = E.alloc<float>(nms_seg_work_floats(E.B, ctx->A, std::max(1, ctx->mc.num_classes)));
+  return E.seg_ws;
+}
+
+// postprocess.nms(padded=True) + clip_boxes over caller-provided candidates (phx_soft_nms, phx_nms_global) under
+// the context's nms_configs; the context's scratch grows on demand (synchronising s)
+void run_nms_candidates(phx_ctx* ctx, const float* boxes, const float* scores, const int* count, int B, int N,
+                        float* ob, float* os, int* oc, int* sel, hipStream_t s) {
+  const NmsSegParams q = ctx->nms_params(ctx->nms_thresh);
+  if (!ctx->nms_hard()) {
+    const size_t need = soft_nms_work_floats(B, N);
+    if (need > ctx->sn_cap) {
+      PHX_HIP(hipStreamSynchronize(s));
+      ctx->sn_ws.reset(dalloc<float>(need));
+      ctx->sn_cap = need;
+    }
+    launch_soft_nms(boxes, scores, nullptr, 0, count, B, N, q.score_thresh, q.soft_sigma, PHX_MAX_OUT,
+                    (float)ctx->mc.image_size, ob, os, oc, (float*)ctx->sn_ws.get(), s, NmsCand{}, sel);
+    launch_nms_truncate(ob, os, oc, sel, B, q.max_out, s);
+    return;
+  }
+  launch_nms_seg_global(boxes, scores, nullptr, 0, count, B, N, q, (float)ctx->mc.image_size, ob, os, oc,
+                        seg_scratch(ctx, B, N, 1, s), s, NmsCand{}, sel);
+}
+
+float* seg_scratch(phx_ctx* ctx, int B, int N, int C, hipStream_t s) {
+  if (!nms_seg_accepts(N)) throw std::runtime_error("nms: too many candidates");
+  const size_t need = nms_seg_work_floats(B, N, C);
+  if (need > ctx->seg_cap) {
+    PHX_HIP(hipStreamSynchronize(s));
+    ctx->seg_ws.reset(dalloc<float>(need));
+    ctx->seg_cap = need;
+  }
+  return static_cast<float*>(ctx->seg_ws.get());
 }
 
 // PHX_GUARD_BYTES: after a step, every executor allocation's guard band must still be 0xA5

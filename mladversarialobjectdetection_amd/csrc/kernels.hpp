@@ -406,6 +406,45 @@ void launch_soft_nms(const float* boxes, const float* scores, const uint8_t* kee
                      int* out_index = nullptr);
 // work floats of launch_soft_nms (compacted candidate boxes, spilled queue keys, anchors, visits)
 size_t soft_nms_work_floats(int B, int N);
+// whether launch_soft_nms takes N positions per image (its LDS plan fits); it throws otherwise
+bool soft_nms_accepts(int N);
+
+// ---- segmented NonMaxSuppressionV5 (kernels_nms_seg.hip): hard NMS and per-class NMS ----------
+// TF's parameters as the op takes them: soft_nms_sigma 0 = hard (sim > iou_thresh drops a candidate)
+struct NmsSegParams {
+  float score_thresh, iou_thresh, soft_sigma;
+  int max_out;  // 1..100; the outputs keep rows of 100
+};
+// N positions per image: the range launch_soft_nms takes; every launcher below throws beyond it, on the host
+bool nms_seg_accepts(int N);
+// work floats (8-byte aligned) of a call over B images of N positions and C segments per image
+size_t nms_seg_work_floats(int B, int N, int C);
+// the segment kernel alone.  Segment b*C+c: seg_cnt entries of image b's list [N] from seg_off (null: 0), each
+// an index into the image's boxes [N,4] / scores [N].  sel_idx / sel_score [B*C,100]: the selections in order
+// (rows >= sel_cnt are not written), sel_cnt [B*C].
+void launch_nms_seg_raw(const float* boxes, const float* scores, const int* list, const int* seg_off,
+                        const int* seg_cnt, int B, int C, int N, const NmsSegParams& q, int* sel_idx,
+                        float* sel_score, int* sel_cnt, float* work, hipStream_t s);
+// one segment per image: launch_soft_nms' arguments and output layout (rows of 100) for any NMS parameters
+void launch_nms_seg_global(const float* boxes, const float* scores, const uint8_t* keep, int keep_mask,
+                           const int* count, int B, int N, const NmsSegParams& q, float clip_hi, float* out_boxes,
+                           float* out_scores, int* out_count, float* work, hipStream_t s, NmsCand cand = NmsCand{},
+                           int* out_index = nullptr);
+// per_class_nms (postprocess.py:409-467): candidates (i < count[b], null: N; score > thresh) grouped by
+// classes [B,N] in [0, C), nms(padded=False) per class, the max_out best by score (ties: class order, then
+// selection order), boxes x scales[b] (null: as they are) and not clipped, classes + 1 as float; out_* rows of
+// 100, zero at and beyond out_count = min(max_out, selections of all classes)
+void launch_nms_seg_per_class(const float* boxes, const float* scores, const int* classes, const int* count, int B,
+                              int N, int C, const NmsSegParams& q, const float* scales, float* out_boxes,
+                              float* out_scores, float* out_classes, int* out_count, float* work, hipStream_t s);
+// launch_soft_nms' outputs (rows of 100) cut to max_out selections: later rows zero, index -1, count capped
+void launch_nms_truncate(float* out_boxes, float* out_scores, int* out_count, int* out_index, int B, int max_out,
+                         hipStream_t s);
+// read-only view of the segment kernel's launch plan for N positions, for the parity harness
+struct NmsSegPlanInfo {
+  int m, nchunk, cap, lds, threads;
+};
+NmsSegPlanInfo nms_seg_plan_info(int N);
 // per-image m_b = max(max_{keep} score, 0), tie count, and loss-gradient coefficient
 void launch_image_max(const float* scores, const uint8_t* keep, int B, int A, float* m,
                       int* argmax, int* nties, int* scratch, hipStream_t s);

@@ -1014,6 +1014,12 @@ __global__ __launch_bounds__(kNmsThreads) void k_soft_nms(
 
 size_t soft_nms_work_floats(int B, int N) { return (size_t)B * N * 7; }
 
+bool soft_nms_accepts(int N) {
+  if (N < 1) return false;
+  const NmsPlan pl = nms_plan(N);
+  return !(pl.lds > kNmsLdsBytes || pl.nchunk > 64 * kNmsGroups);
+}
+
 // PHX_NMS_STATS=1: each image's soft-NMS reports its candidate count, list size, pops and path
 static int nms_debug() {
   static const int v = env_flag("PHX_NMS_STATS") ? 1 : 0;

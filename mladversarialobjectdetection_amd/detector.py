@@ -86,9 +86,12 @@ class ServeDriver:
                             images.data_ptr(), scales.data_ptr(), _stream())
         return images, scales
 
-    def serve(self, frames):
+    def serve(self, frames, post_mode=None):
         """-> (boxes [B,100,4] frame pixels, scores [B,100], classes [B,100] float32 (1 = person),
-        valid_len [B] int32) on the device; rows >= valid_len are zero."""
+        valid_len [B] int32) on the device; rows >= valid_len are zero.  post_mode 'global' or 'per_class'
+        (EfficientDetModel.call's; boxes are not clipped under 'per_class'); None: the context's."""
+        if post_mode is not None and post_mode != self.model.ctx.get_post_mode():
+            self.model.ctx.set_post_mode(post_mode)
         p = self._pack(frames)
         B, dev = len(p.offsets), p.src.device
         boxes = torch.empty(B, _lib.MAX_OUT, 4, device=dev)
@@ -100,7 +103,7 @@ class ServeDriver:
                             _stream())
         return boxes, scores, classes, valid
 
-    def postprocess_global(self, boxes, scores, classes, count=None, scales=None):
+    def postprocess_global(self, boxes, scores, classes, count=None, scales=None, entry="phx_nms_global"):
         """postprocess.postprocess_global (postprocess.py:375-406) over [B,N,4] / [B,N] / [B,N] int32
         candidates (count [B]: valid candidates per row); scales [B] or None (model pixels)."""
         boxes = boxes.contiguous().float()
@@ -116,11 +119,16 @@ class ServeDriver:
         os_ = torch.empty(B, _lib.MAX_OUT, device=dev)
         ocl = torch.empty(B, _lib.MAX_OUT, device=dev)
         oc = torch.empty(B, dtype=torch.int32, device=dev)
-        self.model.ctx.call("phx_nms_global", boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(),
+        self.model.ctx.call(entry, boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(),
                             count.data_ptr() if count is not None else None, B, N,
                             scales.data_ptr() if scales is not None else None, ob.data_ptr(), os_.data_ptr(),
                             ocl.data_ptr(), oc.data_ptr(), _stream())
         return ob, os_, ocl, oc
+
+    def postprocess_per_class(self, boxes, scores, classes, count=None, scales=None):
+        """postprocess.per_class_nms (postprocess.py:409-467) over the same arguments: NMS per class under the
+        context's nms_configs, the max_output_size best of all classes, boxes x scales and not clipped."""
+        return self.postprocess_global(boxes, scores, classes, count, scales, entry="phx_nms_per_class")
 
 
 def _persons(boxes, scores, classes, n, max_boxes):
@@ -142,7 +150,8 @@ class Detector:
     checked against the model table by the library, whose error surfaces) and nms_configs (through
     VictimConfig.override); any other key raises, as override does."""
 
-    def __init__(self, *, params=None, model=MODEL, weights="synthetic", max_batch=1, **victim_kwargs):
+    def __init__(self, *, params=None, model=MODEL, weights="synthetic", max_batch=1, post_mode="global",
+                 **victim_kwargs):
         params = dict(params or {})
         image_size = params.pop("image_size", victim_kwargs.pop("image_size", 0))
         if isinstance(image_size, (tuple, list)):
@@ -158,6 +167,9 @@ class Detector:
         victim = EfficientDetVictim(model, weights, image_size=int(image_size), max_batch=max_batch, **victim_kwargs)
         if nms is not None:
             victim.config.override({"nms_configs": dict(nms)})
+        if post_mode not in _lib.POST_MODES:
+            raise ValueError(f"Detector: post_mode {post_mode!r}: 'global' or 'per_class'")
+        self.post_mode = post_mode
         self.driver = ServeDriver(victim)
 
     def infer(self, frame, max_boxes=200):
@@ -165,9 +177,11 @@ class Detector:
         and their scores, Python lists in NMS order."""
         return self.infer_batch([np.asarray(frame)], max_boxes)[0]
 
-    def infer_batch(self, frames, max_boxes=200):
-        """`infer` for every frame of a batch (<= max_batch) through one phx_serve call."""
-        boxes, scores, classes, valid = (t.cpu().numpy() for t in self.driver.serve(frames))
+    def infer_batch(self, frames, max_boxes=200, post_mode=None):
+        """`infer` for every frame of a batch (<= max_batch) through one phx_serve call; post_mode None: the
+        detector's."""
+        boxes, scores, classes, valid = (t.cpu().numpy()
+                                         for t in self.driver.serve(frames, post_mode or self.post_mode))
         return [_persons(boxes[b], scores[b], classes[b], valid[b], max_boxes) for b in range(len(valid))]
 
     def infer_device(self, frames, min_score_thresh):
@@ -175,7 +189,7 @@ class Detector:
         boxes with score >= float32(min_score_thresh) in NMS order, zero beyond pcount [B] int32;
         best [B] float32 the best person score of each frame, thresholded or not, 0 without a person:
         demo.py:81's max(sc) before the * 100.)."""
-        boxes, scores, classes, valid = self.driver.serve(frames)
+        boxes, scores, classes, valid = self.driver.serve(frames, self.post_mode)
         B, dev = valid.shape[0], valid.device
         pboxes = torch.empty(B, _lib.MAX_OUT, 4, device=dev)
         pcount = torch.empty(B, dtype=torch.int32, device=dev)
