@@ -16,7 +16,7 @@ def build(jobs: int = 8, verbose: bool = False) -> str:
     if r.returncode != 0:
         raise RuntimeError("libphx build failed")
     # the kernel parity checkers link against the library (tests/test_gpu_gemm_kernels.py,
-    # tests/test_gpu_conv_kernels.py, tests/test_gpu_norm_kernels.py, tests/test_gpu_conv3_kernels.py, tests/test_gpu_eot_kernels.py, tests/test_gpu_post_kernels.py and tests/test_gpu_batch_invariance.py run them)
+    # tests/test_gpu_conv_kernels.py, tests/test_gpu_norm_kernels.py, tests/test_gpu_conv3_kernels.py, tests/test_gpu_eot_kernels.py, tests/test_gpu_post_kernels.py, tests/test_gpu_unet_kernels.py and tests/test_gpu_batch_invariance.py run them)
     # (tests/kernels_sefold: the checker of the SE backward without its dx tensor, tests/test_gpu_sefold_kernels.py)
     # (tests/kernels_nms_seg: the checker of the segmented NMS and its host-only teeth program,
     # tests/test_gpu_nms_modes_kernels.py, tests/test_nms_modes_host.py)

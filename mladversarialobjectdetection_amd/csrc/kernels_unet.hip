@@ -660,7 +660,8 @@ __global__ __launch_bounds__(256) void k_un_pool_drop(const float* __restrict__ 
   }
 }
 
-// backward of pool + dropout: dx (the whole input, zeros off the winning taps) [+= when acc]
+// backward of pool + dropout: dx (every window's four taps, zeros off the winning one) [+= when acc]; the
+// last row / column of an odd H / W lies in no window and is never stored (the launcher refuses that without acc)
 __global__ __launch_bounds__(256) void k_un_pool_drop_bwd(const float* __restrict__ dout,
                                                           const uint8_t* __restrict__ arg, float* __restrict__ dx,
                                                           int B, int H, int W, int C, uint64_t seed, int64_t step,
@@ -1109,6 +1110,17 @@ void un_colsum(const float* v, long M, int C, float* out, double* part, hipStrea
 
 size_t un_colred_doubles(long M, int C) { return (size_t)un_colred_blocks(M, C) * C * 2; }
 
+ColredPlanInfo un_colred_plan_info(long M, int C) {
+  if (C < 1 || C > 256) throw std::runtime_error("unet column reduction: C must be in [1, 256]");
+  ColredPlanInfo p{};
+  p.blocks = un_colred_blocks(M, C);
+  p.rows_per_block = (M + p.blocks - 1) / p.blocks;
+  p.lane_rows = 256 / C;
+  p.idle = 256 - p.lane_rows * C;
+  p.last_rows = M - (long)(p.blocks - 1) * p.rows_per_block;
+  return p;
+}
+
 void un_bnact(const float* y, const float* mu, const float* sc, const float* be, float* a, long M, int C, int act,
               hipStream_t st) {
   hipLaunchKernelGGL(k_un_bnact, grid_for(M * C), dim3(256), 0, st, y, mu, sc, be, a, M * C, C, act);
@@ -1124,6 +1136,9 @@ void un_pool_drop(const float* x, float* out, uint8_t* arg, int B, int H, int W,
 
 void un_pool_drop_bwd(const float* dout, const uint8_t* arg, float* dx, int B, int H, int W, int C, uint64_t seed,
                       int64_t step, int gimg0, int layer, bool acc, hipStream_t st) {
+  // an odd H or W leaves the last row / column outside every window: only an accumulating call defines it
+  if (!acc && ((H | W) & 1))
+    throw std::runtime_error("un_pool_drop_bwd: an odd H or W needs acc (the last row / column is never stored)");
   hipLaunchKernelGGL(k_un_pool_drop_bwd, grid_for((long)B * (H / 2) * (W / 2) * C), dim3(256), 0, st, dout, arg, dx, B,
                      H, W, C, seed, step, gimg0, layer, acc ? 1 : 0);
   PHX_LAUNCH_CHECK();

@@ -35,6 +35,16 @@ void un_wgrad(const float* dy, int ldy, const float* x, int ldx, int src, int B,
 
 // ---- BN (training) and column sums: fp64 partials (un_colred_doubles) ----------------------
 size_t un_colred_doubles(long M, int C);
+// the row blocks of a column reduction as the launcher derives them: host only, read-only
+// (tests/kernels/unet_parity)
+struct ColredPlanInfo {
+  int blocks;           // workgroups of k_colred64 (un_colred_blocks)
+  long rows_per_block;
+  int lane_rows;        // rows a workgroup reads per pass: 256 / C lane groups of C threads
+  int idle;             // threads past the last whole group of C
+  long last_rows;       // rows of the last block (<= 0: it starts past M and stores zeros)
+};
+ColredPlanInfo un_colred_plan_info(long M, int C);
 void un_bn_stats(const float* y, long M, int C, const float* gamma, float* mean, float* rstd, float* sc,
                  float* mmean, float* mvar, double* part, hipStream_t st);
 // BN backward through act (1 leaky, 0 identity): dy and the gamma / beta gradients
