@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PHX_ABI_VERSION 3
+#define PHX_ABI_VERSION 4
 
 #define PHX_PATCH_SIZE 640                               /* attacker.py:43 */
 #define PHX_NPATCH (PHX_PATCH_SIZE * PHX_PATCH_SIZE * 3)
@@ -84,7 +84,8 @@ int phx_set_allreduce(phx_ctx* ctx, phx_allreduce_fn fn, void* user);
 /* Per-step metrics written by phx_step_grad (host-readable device or host memory, PHX_NMETRIC
  * floats), the reference's add_metric set, attacker.py:196-207. */
 enum {
-  PHX_M_LOSS = 0,        /* sum_b m_b^2 + scale_loss (+ 1e-5*TV on the rank that owns TV)  */
+  PHX_M_LOSS = 0,        /* sum_b m_b^2 + scale_loss (+ 1e-5*TV on the rank that owns TV)
+                            (+ weight * the box-regression term, phx_set_box_loss)          */
   PHX_M_SCALE_LOSS = 1,  /* sum_b (m_b - s)^2                                              */
   PHX_M_TV = 2,          /* total_variation(patch) (written by the rank that owns TV, else 0)  */
   PHX_M_SUM_M = 3,       /* sum_b m_b      (mean_max_score = SUM_M / B)                    */
@@ -302,6 +303,29 @@ enum { PHX_MATCH_MEAN = 0, PHX_MATCH_HISTOGRAM = 1 };
 int phx_set_matcher(phx_ctx* ctx, int matcher);
 /* HistogramMatcher.call((src, tgt)) (brightness_matcher.py:82-115), same contract as
  * phx_brightness_match: one src per image, no print variation.  P >= 2, H*W >= 2. */
+/* An opt-in box-regression term of the attack objective: the reference's InverseDIOULoss
+ * (regression_loss.py:16-142), which the reference kept but never wired in ("unused ... kept for future
+ * reuse", :7).  The wiring is this library's: inside the tape of PatchAttacker.call,
+ *   loss += weight * InverseDIOULoss()(boxes_pred, boxes)
+ * in phx_step_grad (training) and phx_eval_step (test_step) alike, where boxes_pred are the second pass's
+ * anchors of argmax class 0 that pass filter_valid_boxes(thresh=False) (attacker.py:118-141: the set the
+ * score loss reads) and boxes are the boxes the patches were placed by (the first pass's soft-NMS output, or
+ * the caller's boxes / count).  The module is taken as written (regression_loss.py:27-68, :101-142): per
+ * (gt g, pred p) 1 - diou_loss(b1 = g, b2 = p) with divide_no_nan twice, the pred's width / height clamped at
+ * 0 and the gt's not, the "centres" (ymin + height, xmin + width) and enclose_diag as written; per image
+ * sum_g max_p (0 without a pred) + Keras epsilon 1e-7; the batch value is the sum over images.  Gradient
+ * rules [TF-recall]: reduce_max splits among exact ties; tf.maximum / tf.minimum send a tie to their first
+ * argument (never the pred here) and maximum(0., v) passes only v > 0; divide_no_nan has zero gradient
+ * where its denominator is 0.  The masks are not differentiable: the gradient reaches the network through
+ * decode_box_outputs (tf2/anchors.py:30-58) only, and the box head then runs backward beside the class head.
+ * kind PHX_BOX_LOSS_NONE (the default): every plan, workspace size and result is what it is without this
+ * call.  PHX_DTYPE_F32 contexts only.  A change of kind drops the planned executors (the backward plan and
+ * the gradient arena change; the next call plans again).  PHX_EINVAL with a message: an unknown kind, a
+ * non-finite weight, a PHX_DTYPE_BF16 context; PHX_ESTATE while a phx_set_next batch or its prefetched first
+ * pass is pending. */
+enum { PHX_BOX_LOSS_NONE = 0, PHX_BOX_LOSS_INV_DIOU = 1 };
+int phx_set_box_loss(phx_ctx* ctx, int kind, float weight);
+int phx_get_box_loss(const phx_ctx* ctx, int* kind, float* weight);
 int phx_histogram_match(phx_ctx* ctx, const float* src, int P, const float* tgt, int H, int W,
                         int B, float* out, void* stream);
 /* Its intermediates, for exact tests: hist [B,2,256] int32 (the 256-bin Y histograms of source
@@ -477,6 +501,13 @@ int phx_profile_report(phx_ctx* ctx, char* buf, size_t cap, size_t* needed);
 int phx_debug_last_patched(phx_ctx* ctx, float* out, void* stream);
 /* Last step's per-image max scores m_b [B] and loss-anchor index [B] (device->device). */
 int phx_debug_last_maxscores(phx_ctx* ctx, float* m, int32_t* anchor, void* stream);
+/* Last step's box-regression term (phx_set_box_loss), unweighted: per_image [B] (sum over the image's gts of
+ * max_p + 1e-7, regression_loss.py:54-59), and per (image, gt slot) [B,100] the maximum, its lowest anchor
+ * index and the number of anchors that reach it exactly (slots at or past the image's gt count, and every
+ * slot of an image without a kept anchor: 0, -1, 0).  Any pointer may be NULL (device->device).  PHX_ESTATE
+ * when no step with the term has run. */
+int phx_debug_last_box_loss(phx_ctx* ctx, float* per_image, float* gt_max, int32_t* gt_anchor,
+                            int32_t* gt_nties, void* stream);
 /* Last step's second-pass pre_nms outputs (postprocess.pre_nms, postprocess.py:119-156): per-anchor
  * scores [B,A], classes [B,A] and decoded boxes [B,A,4] (ymin, xmin, ymax, xmax px) — the values
  * the loss's person / validity masks read (attacker.py:118-141).  Any pointer may be NULL

@@ -12,7 +12,7 @@ import json
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 PATCH_SIZE = 640
 NPATCH = PATCH_SIZE * PATCH_SIZE * 3
 NPARAM = NPATCH + 1
@@ -25,6 +25,8 @@ NMETRIC = 9
 BN_LOCAL, BN_FROZEN, BN_SYNC = 0, 1, 2
 DTYPE_F32, DTYPE_BF16 = 0, 1
 MATCH_MEAN, MATCH_HISTOGRAM = 0, 1
+BOX_LOSS_NONE, BOX_LOSS_INV_DIOU = 0, 1  # phx_set_box_loss
+BOX_LOSSES = {None: BOX_LOSS_NONE, "inv_diou": BOX_LOSS_INV_DIOU}
 # phx_adv_patch_dev status bits (phx.h PHX_AP_*)
 AP_REFUSED, AP_OVERFLOW, AP_BADCOUNT = 1, 2, 4
 INGEST_BGR = 1  # phx_ingest flag (phx.h PHX_INGEST_BGR): read channel 2 - c
@@ -113,6 +115,8 @@ _SIGS = [
     ("phx_brightness_match", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("phx_set_matcher", c_int, [c_void_p, c_int]),
+    ("phx_set_box_loss", c_int, [c_void_p, c_int, c_float]),
+    ("phx_get_box_loss", c_int, [c_void_p, POINTER(c_int), POINTER(c_float)]),
     ("phx_histogram_match", c_int,
      [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("phx_histogram_lut", c_int,
@@ -150,6 +154,7 @@ _SIGS = [
     ("phx_profile_report", c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_size_t)]),
     ("phx_debug_last_patched", c_int, [c_void_p, c_void_p, c_void_p]),
     ("phx_debug_last_maxscores", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("phx_debug_last_box_loss", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_debug_last_detections", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("phx_debug_last_image_grad", c_int, [c_void_p, c_void_p, c_void_p]),
     ("phx_debug_tap", c_int, [c_void_p, c_char_p, c_int, c_void_p, c_size_t, c_void_p]),
@@ -292,6 +297,18 @@ class Context:
 
     def get_post_mode(self) -> str:
         return "per_class" if self.lib.phx_get_post_mode(self.h) == POST_PER_CLASS else "global"
+
+    def get_box_loss(self):
+        """(kind, weight) of the box-regression term: kind None or 'inv_diou'."""
+        k, w = c_int(), c_float()
+        self.call("phx_get_box_loss", ctypes.byref(k), ctypes.byref(w))
+        return ("inv_diou" if k.value == BOX_LOSS_INV_DIOU else None), float(w.value)
+
+    def set_box_loss(self, kind, weight: float = 1.0):
+        """phx_set_box_loss: kind None or 'inv_diou' (the reference's InverseDIOULoss), its weight."""
+        if kind not in BOX_LOSSES:
+            raise ValueError(f"box_loss {kind!r}: None or 'inv_diou'")
+        self.call("phx_set_box_loss", BOX_LOSSES[kind], float(weight))
 
     def weight_count(self) -> int:
         return int(self.lib.phx_weight_count(self.h))

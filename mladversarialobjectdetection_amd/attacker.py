@@ -369,14 +369,24 @@ class PatchAttacker:
 
     def __init__(self, model: EfficientDetVictim, initial_patch=None, config_override=None,
                  visualize_freq=200, *, seed=0, learning_rate=1e-2, device=None, matcher="brightness",
-                 summary_writer=None):
-        """summary_writer (summaries.py; None = no summaries, and no launch beyond the step's own): when
+                 summary_writer=None, box_loss=None, box_loss_weight=1.0):
+        """box_loss: None (the reference's objective) or "inv_diou": loss += box_loss_weight *
+        InverseDIOULoss()(second-pass person boxes, placement boxes) (regression_loss.py, which the reference
+        kept but never wired in; phx.h phx_set_box_loss), in train_step and test_step alike; their metric
+        dicts then carry "box_loss", the unweighted batch value.  fp32 victims only.
+        summary_writer (summaries.py; None = no summaries, and no launch beyond the step's own): when
         set, train_step hands vis_images() to it at every step with cur_step % visualize_freq == 0 and
         test_step at every such val step, as the reference's call does (attacker.py:209-213); a
         visualize_freq of 0 or less means never."""
         if matcher not in MATCHERS:
             raise ValueError("matcher must be 'brightness' (the reference's Patcher) or 'histogram'")
         self.matcher = matcher
+        if box_loss not in _lib.BOX_LOSSES:
+            raise ValueError("box_loss must be None or 'inv_diou' (the reference's InverseDIOULoss)")
+        self.box_loss = box_loss
+        self.box_loss_weight = float(box_loss_weight)
+        if box_loss is not None:
+            self.METRICS = self.METRICS + ("box_loss",)
         self.model = model
         self.config = model.config
         if config_override:
@@ -393,9 +403,12 @@ class PatchAttacker:
         # [d patch | d scale | metric row]: one SUM all-reduce per step carries the gradient and the
         # per-rank metric sums (loss, counts, #images; TV only on the rank that adds it), so every
         # rank issues exactly the same collective at the same point of train_step
-        self._red = torch.zeros(_lib.NPARAM + _lib.NMETRIC, device=dev)
+        # (with a box-regression term its unweighted batch value rides behind the metric row, whose length
+        # the ABI pins)
+        self._red = torch.zeros(_lib.NPARAM + _lib.NMETRIC + (box_loss is not None), device=dev)
         self.grad = self._red[:_lib.NPARAM]
-        self.metrics_buf = self._red[_lib.NPARAM:]
+        self.metrics_buf = self._red[_lib.NPARAM:_lib.NPARAM + _lib.NMETRIC]
+        self._box_val = self._red[_lib.NPARAM + _lib.NMETRIC:]  # empty without the term
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
         self.learning_rate = learning_rate
@@ -434,6 +447,21 @@ class PatchAttacker:
         every call that pastes patches selects this attacker's first (a host-side assignment)."""
         self.model.ctx.call("phx_set_matcher", MATCHERS[self.matcher][0])
 
+    def _select_box_loss(self):
+        """The box-regression term is a setting of the shared context too; a change of kind makes the
+        library plan its executors again, so it is set only where it differs."""
+        ctx = self.model.ctx
+        if ctx.get_box_loss() != (self.box_loss, float(np.float32(self.box_loss_weight))):
+            ctx.set_box_loss(self.box_loss, self.box_loss_weight)
+
+    def _read_box_loss(self, B):
+        """The unweighted batch value of the step just issued, behind the metric row."""
+        if self.box_loss is None:
+            return
+        per = torch.empty(B, device=self.params.device)
+        self.model.ctx.call("phx_debug_last_box_loss", per.data_ptr(), None, None, None, _stream())
+        torch.sum(per, 0, keepdim=True, out=self._box_val)
+
     # ---- reference methods -------------------------------------------------------------------
     def first_pass(self, images):
         return self.model.first_pass(images)
@@ -456,6 +484,7 @@ class PatchAttacker:
         else:
             bp, cp, maxb = None, None, 0
         self._select_matcher()
+        self._select_box_loss()
         if not training:
             ob = torch.empty(B, _lib.MAX_OUT, 4, device=images.device)
             os_ = torch.empty(B, _lib.MAX_OUT, device=images.device)
@@ -464,10 +493,12 @@ class PatchAttacker:
                                 int(self.cur_step), self.global_offset(B), int(bool(add_tv)),
                                 self.metrics_buf.data_ptr(), ob.data_ptr(), os_.data_ptr(), oc.data_ptr(),
                                 _stream())
+            self._read_box_loss(B)
             return ob, os_, oc
         self.model.ctx.call("phx_step_grad", images.data_ptr(), B, bp, cp, maxb, self.params.data_ptr(),
                             int(self.cur_step), self.global_offset(B), int(bool(add_tv)), self.grad.data_ptr(),
                             self.metrics_buf.data_ptr(), _stream())
+        self._read_box_loss(B)
         return [self.grad[_lib.NPATCH:], self.grad[:_lib.NPATCH].view(640, 640, 3)]
 
     __call__ = call
@@ -487,9 +518,9 @@ class PatchAttacker:
         ddp.allreduce_sum_(self._red)
 
     def _metric_row(self):
-        """Device row [metric row | scale] of the step just run (scale before the update, as the
-        reference's add_metric(self._scale_regressor) inside call, attacker.py:197)."""
-        return torch.cat([self.metrics_buf, self.params[_lib.NPATCH:]])
+        """Device row [metric row | scale | box-term value, when on] of the step just run (scale before the
+        update, as the reference's add_metric(self._scale_regressor) inside call, attacker.py:197)."""
+        return torch.cat([self.metrics_buf, self.params[_lib.NPATCH:], self._box_val])
 
     @staticmethod
     def _derive(v):
@@ -501,10 +532,13 @@ class PatchAttacker:
         # floats per box, in float32: 1 - 4n / (4d + epsilon)
         asr = float(np.float32(1.0) - np.float32(4.0 * v[_lib.M_ASR_NUM])
                     / (np.float32(4.0 * v[_lib.M_ASR_DEN]) + np.float32(1e-7)))
-        return {"loss": float(v[_lib.M_LOSS]), "scale": scale, "scale_loss": float(v[_lib.M_SCALE_LOSS]),
-                "tv_loss": float(v[_lib.M_TV]), "mean_max_score": mean, "std_max_score": math.sqrt(var),
-                "asr": asr, "asr_to_scale": asr / scale if scale else float("inf"),
-                "patches": float(v[_lib.M_NBOX])}
+        out = {"loss": float(v[_lib.M_LOSS]), "scale": scale, "scale_loss": float(v[_lib.M_SCALE_LOSS]),
+               "tv_loss": float(v[_lib.M_TV]), "mean_max_score": mean, "std_max_score": math.sqrt(var),
+               "asr": asr, "asr_to_scale": asr / scale if scale else float("inf"),
+               "patches": float(v[_lib.M_NBOX])}
+        if len(v) > _lib.NMETRIC + 1:  # the box-regression term's unweighted batch value (summed over ranks)
+            out["box_loss"] = float(v[_lib.NMETRIC + 1])
+        return out
 
     def step_metrics(self):
         """Per-step values of the reference's add_metric set (attacker.py:196-207) for the step
@@ -578,6 +612,7 @@ class PatchAttacker:
         # the batch the previous step prefetched, kept alive until this call (which joins its first
         # pass on the current stream) has been issued
         prev = getattr(self, "_next_keep", None)
+        self._select_box_loss()  # (before a next batch is registered: the setter is refused while one is pending)
         _withdraw_if_refilled(self, lambda: self.model.ctx.call("phx_set_next", None, 0, 0))
         self._next_keep = self._next_rec = None
         if next_inputs is not None and boxes is None:
@@ -610,7 +645,8 @@ class PatchAttacker:
         if summaries.due(self.summary_writer, self._val_step, self.visualize_freq):
             self._summarise(False, self._val_step)
         self._val_step += 1
-        ddp.allreduce_sum_(self.metrics_buf)  # every rank, same point: the metric row's one collective
+        # every rank, same point: the one collective of the metric row (and the box-term value behind it)
+        ddp.allreduce_sum_(self._red[_lib.NPARAM:])
         return self.step_metrics(), preds
 
     def reset_metrics(self):

@@ -20,7 +20,9 @@ def build(jobs: int = 8, verbose: bool = False) -> str:
     # (tests/kernels_sefold: the checker of the SE backward without its dx tensor, tests/test_gpu_sefold_kernels.py)
     # (tests/kernels_nms_seg: the checker of the segmented NMS and its host-only teeth program,
     # tests/test_gpu_nms_modes_kernels.py, tests/test_nms_modes_host.py)
-    for sub in ("kernels", "kernels_sefold", "kernels_nms_seg"):
+    # (tests/kernels_boxloss: the checker of the box-regression term's kernels and its host-only teeth program,
+    # tests/test_gpu_boxloss_kernels.py, tests/test_idiou_oracle.py)
+    for sub in ("kernels", "kernels_sefold", "kernels_nms_seg", "kernels_boxloss"):
         kern = os.path.join(os.path.dirname(HERE), "tests", sub)
         if not os.path.isfile(os.path.join(kern, "Makefile")):
             continue

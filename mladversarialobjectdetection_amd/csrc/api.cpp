@@ -296,6 +296,38 @@ int phx_get_nms_config(const phx_ctx* ctx, phx_nms_config* cfg) {
   return PHX_OK;
 }
 
+int phx_set_box_loss(phx_ctx* ctx, int kind, float weight) {
+  if (!ctx) return PHX_EINVAL;
+  if (kind != PHX_BOX_LOSS_NONE && kind != PHX_BOX_LOSS_INV_DIOU)
+    return fail(ctx, PHX_EINVAL, "box_loss: unknown kind (PHX_BOX_LOSS_NONE or PHX_BOX_LOSS_INV_DIOU)");
+  if (!std::isfinite(weight)) return fail(ctx, PHX_EINVAL, "box_loss: the weight must be finite");
+  if (kind != PHX_BOX_LOSS_NONE && ctx->bf16)
+    return fail(ctx, PHX_EINVAL, "box_loss: the box-regression term runs in PHX_DTYPE_F32 contexts only");
+  if (ctx->pre.pending || ctx->next.images)
+    return fail(ctx, PHX_ESTATE, "box_loss: a phx_set_next prefetch is pending (run its step or withdraw it first)");
+  PHX_TRY(ctx)
+  if (kind != ctx->box_loss && !ctx->execs.empty()) {
+    // the backward plan and the gradient arena change: drop every planned executor (after the device has
+    // drained, so no queued kernel still reads its memory)
+    PHX_HIP(hipSetDevice(ctx->device));
+    PHX_HIP(hipDeviceSynchronize());
+    ctx->last = nullptr;
+    ctx->sum = phx_ctx::Sum{};
+    ctx->execs.clear();
+  }
+  ctx->box_loss = kind;
+  ctx->box_w = weight;
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_get_box_loss(const phx_ctx* ctx, int* kind, float* weight) {
+  if (!ctx) return PHX_EINVAL;
+  if (kind) *kind = ctx->box_loss;
+  if (weight) *weight = ctx->box_w;
+  return PHX_OK;
+}
+
 int phx_set_post_mode(phx_ctx* ctx, int mode) {
   if (!ctx) return PHX_EINVAL;
   if (mode != PHX_POST_GLOBAL && mode != PHX_POST_PER_CLASS)
@@ -685,6 +717,9 @@ int phx_step_grad(phx_ctx* ctx, const float* images, int B, const float* boxes,
   launch_image_max(E.scores, E.keep, B, ctx->A, E.mraw, E.argm, E.nties, E.imax_scratch, s);
   launch_loss(E.mraw, B, params, E.dm, grad + PHX_NPATCH, metrics, s);
   ck_note(E, "image max", E.mraw, (size_t)B * 4, s);
+  // the box-regression term: the kept second-pass boxes against the boxes the patches were placed by
+  if (ctx->box_loss != PHX_BOX_LOSS_NONE)
+    run_box_loss(ctx, E, inject ? E.inj_boxes : lab.boxes, inject ? E.inj_count : lab.count, metrics, s);
   // 4. victim data-gradient -> d(patched images)
   run_backward(ctx, E, E.patched, s);
   if (!side_nms) {
@@ -746,6 +781,8 @@ int phx_eval_step(phx_ctx* ctx, const float* images, int B, const float* boxes, 
   run_pre_nms(ctx, E, s, 1);
   launch_image_max(E.scores, E.keep, B, ctx->A, E.mraw, E.argm, E.nties, E.imax_scratch, s);
   launch_loss(E.mraw, B, params, E.dm, E.dscale_scratch, metrics, s);
+  if (ctx->box_loss != PHX_BOX_LOSS_NONE)
+    run_box_loss(ctx, E, inject ? E.inj_boxes : E.nms1_boxes, inject ? E.inj_count : E.nms1_count, metrics, s);
   run_nms(ctx, E, 1, E.nms2_boxes, E.nms2_scores, E.nms2_count, s);
   launch_count_ge(E.nms2_scores, E.nms2_count, B, PHX_MAX_OUT, 0.5f, metrics + PHX_M_ASR_NUM, s);
   launch_tv(params, PHX_PATCH_SIZE, E.tvs, metrics, add_tv != 0, s);
@@ -953,6 +990,22 @@ int phx_debug_last_detections(phx_ctx* ctx, float* scores, int32_t* classes, flo
   if (scores) PHX_HIP(hipMemcpyAsync(scores, E.scores, n * 4, hipMemcpyDeviceToDevice, s));
   if (classes) PHX_HIP(hipMemcpyAsync(classes, E.classes, n * 4, hipMemcpyDeviceToDevice, s));
   if (boxes) PHX_HIP(hipMemcpyAsync(boxes, E.boxes, n * 16, hipMemcpyDeviceToDevice, s));
+  return PHX_OK;
+  PHX_CATCH(ctx)
+}
+
+int phx_debug_last_box_loss(phx_ctx* ctx, float* per_image, float* gt_max, int32_t* gt_anchor, int32_t* gt_nties,
+                            void* stream) {
+  if (!ctx) return PHX_EINVAL;
+  PHX_TRY(ctx)
+  if (!ctx->last || !ctx->last->bl_valid) throw std::logic_error("no step with the box-regression term has run");
+  Exec& E = *ctx->last;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ng = (size_t)E.B * PHX_MAX_OUT * 4;
+  if (per_image) PHX_HIP(hipMemcpyAsync(per_image, E.bl_img, E.B * 4, hipMemcpyDeviceToDevice, s));
+  if (gt_max) PHX_HIP(hipMemcpyAsync(gt_max, E.bl_max, ng, hipMemcpyDeviceToDevice, s));
+  if (gt_anchor) PHX_HIP(hipMemcpyAsync(gt_anchor, E.bl_anchor, ng, hipMemcpyDeviceToDevice, s));
+  if (gt_nties) PHX_HIP(hipMemcpyAsync(gt_nties, E.bl_nties, ng, hipMemcpyDeviceToDevice, s));
   return PHX_OK;
   PHX_CATCH(ctx)
 }

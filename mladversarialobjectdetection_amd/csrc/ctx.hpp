@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "model.hpp"
 #include "phx.h"
+#include "boxloss.hpp"
 #include "post.hpp"
 #include "unet.hpp"
 
@@ -106,6 +107,15 @@ struct Exec : ExecPlan {
   float *mraw = nullptr, *dm = nullptr;
   int *argm = nullptr, *nties = nullptr;
   int* imax_scratch = nullptr;
+  // box-regression term (phx_set_box_loss; reserved only by an executor planned with it): per (image, gt)
+  // maximum, its lowest anchor and tie count [B,100], the per-image and batch values, the chunk scratch
+  // and the box-predict convs' input-gradient offsets
+  float *bl_max = nullptr, *bl_img = nullptr, *bl_batch = nullptr;
+  int *bl_anchor = nullptr, *bl_nties = nullptr, *bl_scratch = nullptr;
+  long* dxoff_box_dev = nullptr;
+  const float* bl_gt = nullptr;   // the gts of the last step with the term (an executor's or a label slot's)
+  const int* bl_gcount = nullptr;
+  bool bl_valid = false;          // a step with the term has filled the buffers above
   // EOT
   ImgParams* img = nullptr;
   BoxPlace* place = nullptr;  // followed by the int lists
@@ -249,6 +259,10 @@ struct phx_ctx {
   size_t seg_cap = 0;
   uint64_t seed = 0;
   int matcher = PHX_MATCH_MEAN;  // phx_set_matcher: the attack's patch-to-scene matcher
+  // phx_set_box_loss: loss += box_w * InverseDIOULoss()(second-pass boxes, placement boxes); kind NONE:
+  // every plan, buffer and result is what it was before the term existed
+  int box_loss = PHX_BOX_LOSS_NONE;
+  float box_w = 1.0f;
   std::vector<WeightEntry> weights;
   size_t wfloats = 0;
   std::string manifest_json;
@@ -477,8 +491,12 @@ namespace phx {
 // detect; train = false: inference BN and no drop connect; force_frozen: inference BN in a training pass
 void run_forward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s, int pass, int64_t step, int gimg0,
                  bool train = true, bool force_frozen = false);
-// data-gradient of the victim from the sparse class-logit gradient
+// data-gradient of the victim from the sparse class-logit gradient (and, in an executor planned with the
+// box-regression term, the sparse box-logit gradient of the last run_box_loss)
 void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s);
+// the box-regression term over E's second-pass pre_nms outputs and the gts (gt [B,100,4], gcount [B]):
+// values into E.bl_*, box_w * batch value added to metrics[PHX_M_LOSS]
+void run_box_loss(phx_ctx* ctx, Exec& E, const float* gt, const int* gcount, float* metrics, hipStream_t s);
 // nms_t of run_pre_nms / run_nms: the context's NMS score threshold (a hard NMS's may be -inf, so no
 // real value can stand for it)
 constexpr float kNmsCtxThresh = std::numeric_limits<float>::quiet_NaN();

@@ -93,6 +93,18 @@ void alloc_exec(Exec& E, int A) {
   E.argm = E.alloc<int>(B);
   E.nties = E.alloc<int>(B);
   E.imax_scratch = E.alloc<int>(image_max_scratch_ints(B));
+  if (P.box_grad) {
+    const size_t ng = (size_t)B * kIdiouMaxGt;
+    E.bl_max = E.alloc<float>(ng);
+    E.bl_anchor = E.alloc<int>(ng);
+    E.bl_nties = E.alloc<int>(ng);
+    E.bl_img = E.alloc<float>(B);
+    E.bl_batch = E.alloc<float>(1);
+    E.bl_scratch = E.alloc<int>(idiou_scratch_ints(B, A));
+    E.dxoff_box_dev = E.alloc<long>(nlev);
+    if ((int)E.dxoff_box.size() != nlev) throw std::logic_error("box loss: no box-predict gradient offsets in the plan");
+    PHX_HIP(hipMemcpy(E.dxoff_box_dev, E.dxoff_box.data(), nlev * sizeof(long), hipMemcpyHostToDevice));
+  }
   // EOT
   const int S = E.ed.H;
   const long nslot = (long)B * PHX_MAX_OUT;
@@ -154,7 +166,8 @@ Exec& phx_ctx::exec_for(int B, int tag) {
     sum_clobber(*execs[lru]);
     execs.erase(execs.begin() + (long)lru);
   }
-  auto ex = std::make_unique<Exec>(plan_exec(mc, B, tag, bn_mode, bf16, A));
+  // (the box-regression term changes the step executor's backward plan only: tags 1 and 2 run forwards)
+  auto ex = std::make_unique<Exec>(plan_exec(mc, B, tag, bn_mode, bf16, A, tag == 0 && box_loss != PHX_BOX_LOSS_NONE));
   alloc_exec(*ex, A);
   ex->used = clock;
   execs.push_back(std::move(ex));
@@ -823,13 +836,21 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
   int K = 0;
   long wpred = -1;
   std::vector<std::pair<char*, size_t>> zero;  // the levels' gradient buffers, merged where adjacent
+  int Kb = 0;
+  long wbox = -1;
   for (int l = 0; l < (int)P.cls_out.size(); ++l) {
     for (const Op& op : P.ops) {
-      if (op.out != P.cls_out[l]) continue;
+      const bool box = P.box_grad && op.out == P.box_out[l];
+      if (op.out != P.cls_out[l] && !box) continue;
       const Tensor& ti = P.tensors[op.in[0]];
       zero.emplace_back(reinterpret_cast<char*>(E.gptr(op.in[0])), ti.numel() * sizeof(float));
-      K = ti.c;
-      wpred = op.w;
+      if (box) {
+        Kb = ti.c;
+        wbox = op.w;
+      } else {
+        K = ti.c;
+        wpred = op.w;
+      }
     }
   }
   std::sort(zero.begin(), zero.end());
@@ -853,11 +874,19 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
   launch_cls_scatter(E.scores, E.keep, E.mraw, E.nties, E.dm, E.tptr(P.cls_out[0], input),
                      E.lev_dev, (int)E.lev.size(), ctx->A, E.B, ctx->mc.num_classes, na,
                      W + wpred, K, E.grad, E.dxoff_dev, s, E.tbf(P.cls_out[0]));
+  // 1b. the box-regression term's sparse gradient into the inputs of the box-predict pointwise convs
+  if (P.box_grad) {
+    if (!E.bl_valid || ctx->box_loss == PHX_BOX_LOSS_NONE) throw std::logic_error("box loss: backward without its forward");
+    Scope scope(ctx, "box_scatter", 0.0, (double)E.B * (ctx->A / na) * 4.0, s);
+    launch_box_scatter(E.boxes, E.keep, E.bl_gt, E.bl_gcount, E.bl_max, E.bl_anchor, E.bl_nties,
+                       E.tptr(P.box_out[0], input), reinterpret_cast<const float*>(ctx->d_anchors.get()), E.lev_dev,
+                       (int)E.lev.size(), ctx->A, E.B, na, W + wbox, Kb, ctx->box_w, E.grad, E.dxoff_box_dev, s);
+  }
   // 2. reverse sweep
   for (int i = (int)P.ops.size() - 1; i >= 0; --i) {
     const Op& op = P.ops[i];
     if (!op.bwd) continue;
-    if (op.t == OP_PW && is_cls_out(P, op.out)) continue;  // handled by the scatter
+    if (op.t == OP_PW && is_scatter_out(P, op.out)) continue;  // handled by the scatters
     if (i > 0 && E.sepb[i - 1]) continue;  // (the pointwise half of a fused sepconv: with its depthwise op)
     if (E.grp_of[i] >= 0) {
       if (E.groups[E.grp_of[i]].back() == i) {
@@ -1027,6 +1056,19 @@ void run_backward(phx_ctx* ctx, Exec& E, const float* input, hipStream_t s) {
     if (gsk.part) E.gstat_region[i - 1] = 0;
     ck_bwd(E, i, s);
   }
+}
+
+// InverseDIOULoss (regression_loss.py:27-68) of the second pass's kept anchors against the gts
+void run_box_loss(phx_ctx* ctx, Exec& E, const float* gt, const int* gcount, float* metrics, hipStream_t s) {
+  if (!E.prog.box_grad) throw std::logic_error("box loss: the executor was planned without it");
+  // algorithmic bytes: every decoded box and keep flag once, the gts, the chunk partials written and read
+  Scope scope(ctx, "idiou", 0.0,
+              (double)E.B * ctx->A * 17.0 + (double)E.B * kIdiouMaxGt * (16.0 + 24.0 * idiou_chunks(ctx->A)), s);
+  launch_idiou(E.boxes, E.keep, gt, gcount, E.B, ctx->A, E.bl_max, E.bl_anchor, E.bl_nties, E.bl_img, E.bl_batch,
+               E.bl_scratch, ctx->box_w, metrics, s);
+  E.bl_gt = gt;
+  E.bl_gcount = gcount;
+  E.bl_valid = true;
 }
 
 // cand_mask: the keep bits whose anchors (above the NMS threshold) pre_nms appends to the

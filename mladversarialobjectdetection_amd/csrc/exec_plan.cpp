@@ -15,6 +15,11 @@ bool is_cls_out(const Program& P, int t) {
   return std::find(P.cls_out.begin(), P.cls_out.end(), t) != P.cls_out.end();
 }
 
+bool is_scatter_out(const Program& P, int t) {
+  if (is_cls_out(P, t)) return true;
+  return P.box_grad && std::find(P.box_out.begin(), P.box_out.end(), t) != P.box_out.end();
+}
+
 namespace {
 
 // ---- level-batched heads -----------------------------------------------------------------
@@ -117,7 +122,7 @@ void plan_groups(ExecPlan& E, bool local_bn) {
     if (!P.ops[i].bwd) continue;
     for (int c = i + 1; c < n && ok; ++c) {
       const Op& oc = P.ops[c];
-      if (!oc.bwd || (oc.t == OP_PW && is_cls_out(P, oc.out))) continue;
+      if (!oc.bwd || (oc.t == OP_PW && is_scatter_out(P, oc.out))) continue;
       for (int j = 0; j < oc.nin; ++j) {
         if (oc.in[j] == P.ops[i].out && bpos(c) <= bpos(i)) ok = false;
         for (int k = 0; k < P.ops[i].nin; ++k)
@@ -145,8 +150,9 @@ bool dw_same_3x3(const Program& P, const Op& d) {
 // the serving executor (tag 2) is planned as a bn=frozen context plans: inference BN only
 static bool batch_bn(int tag, int bn_mode) { return tag == 2 ? false : bn_mode != PHX_BN_FROZEN; }
 
-ExecPlan plan_exec(const ModelConfig& mc, int B, int tag, int bn_mode, bool bf16, int num_anchors) {
+ExecPlan plan_exec(const ModelConfig& mc, int B, int tag, int bn_mode, bool bf16, int num_anchors, bool box_grad) {
   NetBuilder nb(mc, B, batch_bn(tag, bn_mode));
+  nb.set_box_grad(box_grad);
   nb.build();
   return plan_program(nb.program(), B, tag, bn_mode, bf16, mc.image_size, mc.num_anchors(), num_anchors);
 }
@@ -231,7 +237,7 @@ ExecPlan plan_program(const Program& prog, int B, int tag, int bn_mode, bool bf1
         np = dw_bwd_partials(li.n, li.h, li.w, li.c, lo.h, lo.w, L.k, L.stride, L.pad_t, L.pad_l);
       else if (L.t == OP_SE && L.in[0] == bn.out)
         np = ew_gstats_partials((long)li.h * li.w, li.c, li.n);
-      else if (L.t == OP_PW && L.in[0] == bn.out && !is_cls_out(P, L.out))
+      else if (L.t == OP_PW && L.in[0] == bn.out && !is_scatter_out(P, L.out))
         np = gemm_dgrad_gsink_partials((int)li.rows(), li.c, lo.c, bf16);
       else if (L.t == OP_ADD && (L.in[0] == bn.out || L.in[1] == bn.out) && L.in[0] != L.in[1])
         np = ew_gstats_partials((long)tz.rows(), tz.c, 1);
@@ -325,7 +331,7 @@ ExecPlan plan_program(const Program& prog, int B, int tag, int bn_mode, bool bf1
         const Op& d = P.ops[di];
         const Op& pw = P.ops[di + 1];
         const int bi = E.bn_consumer[pw.out];
-        ok = ok && d.bwd && pw.bwd && !is_cls_out(P, pw.out) && bi >= 0 && P.ops[bi].bwd &&
+        ok = ok && d.bwd && pw.bwd && !is_scatter_out(P, pw.out) && bi >= 0 && P.ops[bi].bwd &&
              sep_bwd_supported(P.tensors[d.in[0]].c, P.tensors[pw.out].c, E.bf16 || E.abf);
         ok = ok && (di > 0 && E.gfused_bn[di - 1]) == (mem[0] > 0 && E.gfused_bn[mem[0] - 1]);
       }
@@ -389,6 +395,10 @@ ExecPlan plan_program(const Program& prog, int B, int tag, int bn_mode, bool bf1
     // input of the class-predict pointwise conv
     for (const Op& op : P.ops)
       if (op.out == P.cls_out[l]) E.dxoff.push_back(P.tensors[op.in[0]].goff);
+    // ... and of the box-predict pointwise conv, where the box head runs backward
+    if (P.box_grad)
+      for (const Op& op : P.ops)
+        if (op.out == P.box_out[l]) E.dxoff_box.push_back(P.tensors[op.in[0]].goff);
   }
   if (a0 != num_anchors) throw std::runtime_error("anchor count mismatch");
   // EOT

@@ -63,6 +63,7 @@ struct ExecPlan {
   int n_mov = 0, mov_cmax = 1;
   std::vector<LevelDesc> lev;                  // class / box outputs per level
   std::vector<long> dxoff;                     // gradient offset of each class-predict conv's input
+  std::vector<long> dxoff_box;                 // ... of each box-predict conv's input (Program::box_grad only)
   int ntiles = 0;
   // drop connect (non-b0 backbones, training): per drop op its block id and survival
   int ndrop = 0;
@@ -80,7 +81,10 @@ struct ExecPlan {
 // Throws std::runtime_error("anchor count mismatch") when the program's levels do not add up to
 // num_anchors (the context's anchor table).  PHX_SEP, PHX_SEP_MINROWS, PHX_SEPB and PHX_SEFOLD are read at every
 // call, PHX_FOLD and PHX_GROUP once per process.
-ExecPlan plan_exec(const ModelConfig& mc, int B, int tag, int bn_mode, bool bf16, int num_anchors);
+// box_grad: the backward plan reaches the box head too (phx_set_box_loss); off, the plan is what it was
+// before the term existed.
+ExecPlan plan_exec(const ModelConfig& mc, int B, int tag, int bn_mode, bool bf16, int num_anchors,
+                   bool box_grad = false);
 
 // The planner proper, over a program built elsewhere (plan_exec builds the model's; a test can hand
 // it one made by hand).  na: anchors per cell.
@@ -89,5 +93,8 @@ ExecPlan plan_program(const Program& prog, int B, int tag, int bn_mode, bool bf1
 
 // t is one of the class heads' per-level outputs
 bool is_cls_out(const Program& P, int t);
+// t is a head output whose predict conv's input gradient a sparse scatter writes (its dgrad is skipped):
+// a class output, or a box output of a program with box_grad
+bool is_scatter_out(const Program& P, int t);
 
 }  // namespace phx

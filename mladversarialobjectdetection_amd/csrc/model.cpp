@@ -489,11 +489,13 @@ void NetBuilder::build() {
 // Static backward plan: which ops run, which input grads are overwritten vs accumulated.
 // Only the class head carries a loss gradient (the box outputs feed non-differentiable
 // masks, attacker.py:132-140), so the box head and everything reachable only through it is
-// pruned.
+// pruned — unless a box-regression term is on (Program::box_grad), which seeds the box outputs too.
 void NetBuilder::plan_backward() {
   auto& T = prog_.tensors;
   std::vector<char> has(T.size(), 0);
   for (int t : prog_.cls_out) has[t] = 1;
+  if (prog_.box_grad)
+    for (int t : prog_.box_out) has[t] = 1;
   // reverse sweep: an op runs backward iff its output receives a gradient
   for (int i = (int)prog_.ops.size() - 1; i >= 0; --i) {
     Op& op = prog_.ops[i];

@@ -105,6 +105,9 @@ struct Program {
   int n_slots = 0;                     // BN + SE statistics slots
   std::vector<int> slot_channels;      // channels per slot
   int batch = 0;
+  // the box outputs carry a loss gradient too (phx_set_box_loss): plan_backward seeds them and the
+  // box head runs backward
+  bool box_grad = false;
 };
 
 // Walks the victim architecture.  With batch == 0 only the weight manifest is produced.
@@ -112,6 +115,8 @@ class NetBuilder {
  public:
   // training: drop-connect active (attack step, training=True); ignored when batch == 0
   NetBuilder(const ModelConfig& cfg, int batch, bool training = true);
+  // before build(): the backward plan reaches the box head as well (a box-regression loss term)
+  void set_box_grad(bool on) { prog_.box_grad = on; }
   void build();
   const std::vector<WeightEntry>& weights() const { return weights_; }
   size_t weight_floats() const { return wfloats_; }
